@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """MLM pretraining throughput of DNABERT-2-117M at seq_len 512 on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--dump-outputs DIR] [--full]
     N > 1: either under a launcher (python -m torch.distributed.run --nproc-per-node N ...
     bench.py --gpus N ...) or plain `bench.py --gpus N`, which starts the N rank processes itself
     (rank r on cuda:r, RCCL; DNA_DIST_BACKEND=gloo rehearses it with every rank on one GPU).
@@ -12,7 +12,11 @@ BPE tokens each, BERT 15 % masking), random-init weights of the 117,074,176-para
 architecture, bf16 compute, dropout 0.1. Batches are tokenised/masked on the host before timing
 and sit in HBM; K steps are timed between barrier + synchronize, max over ranks.
 Prints ONE JSON line (rank 0) with the roofline of the dominant kernel (HIP events on the launch
-stream over the timed region) and the CPU baseline (oracle restatement on this host's cores).
+stream over the timed region). A plain run does only that: set up, warm up, time the K steps.
+--dump-outputs DIR then writes what the last timed step handed back (dump_outputs below).
+--full adds the measurements that take runs of their own: the host data pipeline, the per-GPU
+b=64 line and the CPU baselines (oracle restatement on this host's cores); each keeps its --no-*
+switch.
 """
 import argparse
 import json
@@ -153,6 +157,26 @@ def cpu_baseline(seconds_budget=10.0, threads=None, cfg=None, seq=None, batch=2,
                       f"{t_used:.1f} s timed"}
 
 
+DUMP_SAMPLE = 1 << 22  # elements of each flat buffer kept by --dump-outputs (16 MB as float32)
+
+
+def dump_outputs(out_dir, trainer, loss):
+    """What a caller of the timed path holds after its last step, as float32 <name>.npy files:
+    the step's loss, and a fixed (seed 0) sample of DUMP_SAMPLE positions of the updated flat
+    parameter buffer and of the flat gradient buffer the step left (whole, when they are smaller)."""
+    os.makedirs(out_dir, exist_ok=True)
+    n = trainer.flat.numel
+    if n > DUMP_SAMPLE:
+        pos = np.sort(np.random.default_rng(0).choice(n, size=DUMP_SAMPLE, replace=False))
+        pos = torch.from_numpy(pos).to(trainer.flat.flat.device)
+        take = lambda t: t.index_select(0, pos)
+    else:
+        take = lambda t: t
+    np.save(os.path.join(out_dir, "loss.npy"), loss.detach().float().reshape(1).cpu().numpy())
+    np.save(os.path.join(out_dir, "params_sample.npy"), take(trainer.flat.flat).cpu().numpy())
+    np.save(os.path.join(out_dir, "grads_sample.npy"), take(trainer.flat.grad).cpu().numpy())
+
+
 # BASELINE configs[0] / SURVEY §8(d) config A: 2 layers, d_model 128, 2 heads, S = 128, batch 8
 CONFIG_A = dict(vocab_size=4096, hidden_size=128, num_hidden_layers=2, num_attention_heads=2,
                 intermediate_size=512)
@@ -189,6 +213,12 @@ def main():
     ap.add_argument("--steps", type=int, default=100)   # 100 timed, 20 warm-up
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--batch", type=int, default=int(os.environ.get("DNA_BENCH_BATCH", 512)))
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the last timed step's loss and a fixed sample of the updated "
+                         "parameters and gradients as DIR/<name>.npy (rank 0)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the host data pipeline, the per-GPU b=64 line and the CPU "
+                         "baselines (runs of their own, outside the headline figure)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-kernel-timing", action="store_true")
     ap.add_argument("--no-b64", action="store_true", help="skip the extra per-GPU b=64 measurement")
@@ -198,6 +228,8 @@ def main():
     ap.add_argument("--dist-dry-run", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--dump-params", default=None, help=argparse.SUPPRESS)  # debug: per-rank digest
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1 (the timed steps are the measurement)")
     # the timed step must stay on the hand-written kernels: any torch/hipBLASLt GEMM fallback in
     # dna_amd.functional raises (DNA_STRICT_NATIVE=0 turns the check off for experiments)
     os.environ.setdefault("DNA_STRICT_NATIVE", "1")
@@ -222,7 +254,7 @@ def main():
         return dist_skeleton(args, world, rank, result_out)
 
     data_pipeline = None
-    if rank == 0 and world == 1 and not args.no_data_pipeline:
+    if args.full and rank == 0 and world == 1 and not args.no_data_pipeline:
         # train.py's own data path, timed before this process touches the GPU (its DataLoader
         # workers fork from a clean process; the H2D leg then brings HIP up) -- not part of value
         data_pipeline = measure_data_pipeline(args.batch, torch.device("cuda", local))
@@ -275,6 +307,8 @@ def main():
         all_reduce_(elapsed, op=dist.ReduceOp.MAX)
     elapsed = float(elapsed.item())
     final_loss = float(loss.item())
+    if args.dump_outputs and rank == 0:  # before anything below steps the trainer again
+        dump_outputs(args.dump_outputs, trainer, loss)
 
     seqs = args.batch * args.steps * world
     value = seqs / elapsed
@@ -282,7 +316,7 @@ def main():
 
     # besides the best per-GPU batch, always report b=64
     b64 = None
-    if args.batch != 64 and not args.no_b64:
+    if args.full and args.batch != 64 and not args.no_b64:
         bb = make_batches(2, 64, rank, device)
         for i in range(3):
             trainer.step(bb[i % 2])
@@ -336,7 +370,7 @@ def main():
             roofline["traffic_source"] = traffic[dom]["source"]
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline()
         one = cpu_baseline(seconds_budget=10.0, threads=1)  # the reference forces OMP_NUM_THREADS=1
         cpu["single_thread"] = {"value": one["value"], "cores": 1, "sample": one["sample"]}

@@ -8,7 +8,7 @@
 #   bash scripts/gpu.sh bench [bench.py args...]      one bench line -> gpurun_out/bench.json
 #   bash scripts/gpu.sh round ROUND [BATCH]           the round bundle: rocprofv3 --stats of the
 #        bench, FETCH_SIZE / WRITE_SIZE passes -> profiles/ROUND/traffic.json, the
-#        rocprof-vs-HIP-event agreement table, then the default bench line
+#        rocprof-vs-HIP-event agreement table, then the `bench.py --full` line
 #   bash scripts/gpu.sh ab-env VAR "v1 v2 ..." [REPS]  interleaved bench A/B of an env switch
 #   bash scripts/gpu.sh ab-lib "main base ..." [REPS] [STEPS]  interleaved bench A/B of library
 #        builds (scripts/build_variant.sh REV NAME -> dna_amd/lib/libdna_amd_NAME.so)
@@ -44,7 +44,7 @@ round)
   mkdir -p "$OUT" "$ROOT/profiles/$R"
   cd /tmp && export TMPDIR=/tmp
   timeout -k 10 600 rocprofv3 --kernel-trace --stats -d $OUT/stats -o run --output-format csv -- \
-    python $ROOT/bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-b64 --batch $BATCH \
+    python $ROOT/bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-b64 --batch $BATCH \
     > $OUT/stats_bench.json 2> $OUT/stats_bench.err
   for c in FETCH_SIZE WRITE_SIZE; do
     d=$(echo $c | cut -d_ -f1 | tr A-Z a-z)
@@ -59,7 +59,7 @@ round)
   python $ROOT/scripts/roofline_agree.py $OUT/stats/run_kernel_stats.csv $OUT/stats_bench.json 13 \
     > $OUT/roofline_agreement.md
   cd $ROOT
-  timeout -k 10 600 python bench.py --batch $BATCH > $OUT/bench.json 2> $OUT/bench.err
+  timeout -k 10 600 python bench.py --full --batch $BATCH > $OUT/bench.json 2> $OUT/bench.err
   rm -rf $OUT/fetch $OUT/write
   ;;
 ab-env)
