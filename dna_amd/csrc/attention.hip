@@ -1467,11 +1467,12 @@ constexpr size_t bwd3_lds() {
 #endif
 #if DNA_BWD3_STAMP
 // timing probe (debug builds only): s_memtime at phase boundaries of block 0's waves
-__device__ unsigned long long g_bwd3_stamps[4][16][6];
+__device__ unsigned long long g_bwd3_stamps[8][17][6];  // [wave][slice][stamp]; the 4-wave kernel fills waves
+// 0-3. Row 16: kernel entry, slice loop entry, loop exit, dK/dV stored, kernel end
 #define BWD3_STAMP(t, k)                                                              \
   do {                                                                                \
     const unsigned long long ts_ = __builtin_amdgcn_s_memtime();                     \
-    if (blockIdx.x == 0 && lane == 0 && (t) < 16) g_bwd3_stamps[wave][(t)][(k)] = ts_; \
+    if (blockIdx.x == 0 && lane == 0 && (t) < 17) g_bwd3_stamps[wave][(t)][(k)] = ts_; \
   } while (0)
 #else
 #define BWD3_STAMP(t, k) do {} while (0)
@@ -1513,6 +1514,7 @@ __global__ __launch_bounds__(256, 1) void bwd3_bf16_kernel(
   const float invc = 1.f / c;
   const float sl_t = slope2 * invc;
   const float* lse_bh = lse + ((size_t)b * H + h) * S;
+  BWD3_STAMP(16, 0);
 
   {  // K image of all S keys
     constexpr int NCH = S * 8 / 256;
@@ -1597,6 +1599,7 @@ __global__ __launch_bounds__(256, 1) void bwd3_bf16_kernel(
     store_slice(0, 0, x, tid);
   }
   __syncthreads();
+  BWD3_STAMP(16, 1);
 
   for (int t = 0; t < NS; ++t) {
     BWD3_STAMP(t, 0);
@@ -1791,6 +1794,7 @@ __global__ __launch_bounds__(256, 1) void bwd3_bf16_kernel(
     }
     BWD3_STAMP(t, 5);
   }
+  BWD3_STAMP(16, 2);
 
   // ---- dK, dV rows of this wave's keys
 #pragma unroll
@@ -1814,6 +1818,7 @@ __global__ __launch_bounds__(256, 1) void bwd3_bf16_kernel(
         *reinterpret_cast<bf16x4*>(row + 2 * H * D + 32 * dt + 8 * g + 4 * hh) = vv;
       }
   }
+  BWD3_STAMP(16, 3);
   if (DBE) {  // column sums per 128 keys: per-wave sums via LDS, then 4/KB waves per row
     // re-read the accumulators below instead of keeping the 256 values read for the stores live
 #pragma unroll
@@ -1884,6 +1889,474 @@ __global__ __launch_bounds__(256, 1) void bwd3_bf16_kernel(
       dbias_part[((size_t)b * KB + j) * ld + ts * H * D + h * D + d] = sum;
     }
   }
+  BWD3_STAMP(16, 4);
+}
+
+// LDS access by 32-bit byte address (the 8-wave kernel forms its addresses as integers)
+typedef __attribute__((address_space(3))) char lds_byte;
+__device__ __forceinline__ unsigned lds_addr(const void* p) { return (unsigned)(size_t)(lds_byte*)p; }
+template <typename T>
+__device__ __forceinline__ T lds_ld(unsigned a) {
+  return *(const __attribute__((address_space(3))) T*)(size_t)a;
+}
+template <typename T>
+__device__ __forceinline__ void lds_st(unsigned a, T v) {
+  *(__attribute__((address_space(3))) T*)(size_t)a = v;
+}
+__device__ __forceinline__ bf16x4 tr_read_a(unsigned a) {
+  s16x4 v = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(size_t)a);
+  return __builtin_bit_cast(bf16x4, v);
+}
+
+// ----------------------------------------------------------------------------- bf16 backward, v3, 8 waves
+// The same fused pass with 8 waves per workgroup, two per SIMD, for S = 256*KB (KB = 1, 2): wave w
+// owns keys [w*32*KB, (w+1)*32*KB). A partner wave on the SIMD takes the matrix pipe while this
+// one is in its softmax tail, an LDS wait or a barrier, so phase 1 is not software-pipelined: a
+// wave's key blocks run one after the other (S'/dP' MFMAs, exp and dS, the dS^T image, then the
+// block's dV/dK MFMAs), nothing is carried between blocks, and the Q / dO fragments are re-read
+// per block. That brings a wave to 128 VGPRs beside its 4*KB pinned accumulators.
+//  phase 2: dQ^T = K^T dS^T split as (32-d half) x (key quarter); the four quarter partials are
+//    summed through LDS as (q0 + q1) + (q2 + q3), each wave finishing one register group.
+//  dK, dV and the bias-gradient partial rows are bit-identical to the 4-wave kernel's: the sums
+//    over the query slices are per key and unchanged, and the epilogue's column sums chain waves
+//    2j, 2j+1 (the keys of one 4-wave-kernel wave) in that kernel's order.
+// LDS: K image | Q/dO images | dS^T image | row constants | red (dQ partials, [2 dth][4 src
+// quarter][3 groups][256]) | sigl | cs. The epilogue's four [64][CS_LD] staging images reuse the
+// bytes from the Q image on (dead by then), and must end before sigl.
+template <int KB>
+constexpr size_t bwd8_red_off() {
+  return (size_t)256 * KB * D * 2 + 4 * 32 * D * 2 + (size_t)256 * KB * 32 * 2 + 2 * 4 * 32 * 4;
+}
+constexpr size_t BWD8_RED = 2 * 4 * 3 * 256 * 4;
+template <int KB>
+constexpr size_t bwd8_sig_off() {
+  constexpr size_t a = bwd8_red_off<KB>() + BWD8_RED;
+  constexpr size_t st_end = (size_t)256 * KB * D * 2 + 4 * 64 * CS_LD * 4;
+  return a > st_end ? a : st_end;
+}
+template <int KB>
+constexpr size_t bwd8_lds() { return bwd8_sig_off<KB>() + (size_t)256 * KB * 2 * 4 + 4 * 3 * 64 * 4; }
+
+#if DNA_BWD3_STAMP
+#define BWD8_STAMP(t, k) BWD3_STAMP(t, k)
+#else
+#define BWD8_STAMP(t, k) do {} while (0)
+#endif
+// DB: fused bias-gradient column sums. (A static s_setprio 1 for waves 4-7 over the slice loop
+// was measured and not kept: attn_bwd 1.713 -> 1.753 ms in the bench.)
+template <int KB, bool DB>
+__global__ __launch_bounds__(512, 2) void bwd3w8_bf16_kernel(
+    const bf16* __restrict__ qkv, const bf16* __restrict__ out, const bf16* __restrict__ dout,
+    const float* __restrict__ lse, const uint8_t* __restrict__ key_valid,
+    const float* __restrict__ slopes, int H, float c, float scale, bf16* __restrict__ dqkv,
+    float* __restrict__ dbias_part) {
+  static_assert(KB == 1 || KB == 2, "8 waves x 32*KB keys: S = 256 or 512");
+  static_assert(bwd8_lds<KB>() <= 160 * 1024, "LDS map");
+  constexpr int S = 256 * KB;   // keys = queries of one (batch, head)
+  constexpr int KPW = 32 * KB;  // keys per wave
+  constexpr int NS = S / 32;    // query slices
+  constexpr int KS2 = S / 64;   // 16-key steps of one key quarter (phase 2)
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  bf16* Kimg = reinterpret_cast<bf16*>(smem);          // [S][64] swz
+  bf16* Qimg = Kimg + S * D;                            // [2][32][64] swz
+  bf16* Oimg = Qimg + 2 * 32 * D;                       // [2][32][64] dO, swz
+  bf16* dST = Oimg + 2 * 32 * D;                        // [S][32] dS^T, 8-B chunks XOR (row>>1)&7
+  float* rc = reinterpret_cast<float*>(dST + S * 32);  // [2][4][32] row constants
+  float* red = reinterpret_cast<float*>(smem + bwd8_red_off<KB>());
+  float* sigl = reinterpret_cast<float*>(smem + bwd8_sig_off<KB>());  // [2 hh][S] dS row sums
+
+  const int bh = blockIdx.x, h = bh % H, b = bh / H;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int kl = lane & 31, hh = lane >> 5;
+  const int g16 = lane >> 4, i16 = lane & 15;
+  const int ld = 3 * H * D;
+  const bf16* base = qkv + (size_t)b * S * ld;
+  const size_t obase = (size_t)b * S * (H * D) + h * D;
+  const float slope2 = slopes[h] * LOG2E;
+  const float invc = 1.f / c;
+  const float sl_t = slope2 * invc;
+  const float* lse_bh = lse + ((size_t)b * H + h) * S;
+  BWD8_STAMP(16, 0);
+
+  {  // K image of all S keys
+    constexpr int NCH = S * 8 / 512;
+    bf16x8 kt[NCH];
+#pragma unroll
+    for (int i = 0; i < NCH; ++i) {
+      const int cc = tid + 512 * i;
+      kt[i] = *reinterpret_cast<const bf16x8*>(base + (size_t)(cc >> 3) * ld + H * D + h * D + (cc & 7) * 8);
+    }
+#pragma unroll
+    for (int i = 0; i < NCH; ++i) {
+      const int cc = tid + 512 * i;
+      *reinterpret_cast<bf16x8*>(Kimg + swz(cc >> 3, (cc & 7) * 8)) = kt[i];
+    }
+  }
+  // V of one key block as the B operand of dP' (key on the lane). Only the current block's
+  // fragments are held: with KB = 2 the other block's are fetched again (L2-hot) as soon as the
+  // S'/dP' MFMAs have taken these, and land under the block's softmax tail and dV/dK MFMAs
+  bf16x8 vf[4];
+  const bf16* vbase = base + 2 * H * D + h * D;
+#pragma unroll
+  for (int s = 0; s < 4; ++s)
+    vf[s] = *reinterpret_cast<const bf16x8*>(vbase + (size_t)(wave * KPW + kl) * ld + 8 * hh + 16 * s);
+  unsigned padm = 0;  // bit kb: key wave*KPW + 32kb + kl is a pad key
+#pragma unroll
+  for (int kb = 0; kb < KB; ++kb)
+    if (key_valid && !key_valid[(size_t)b * S + wave * KPW + 32 * kb + kl]) padm |= 1u << kb;
+
+  // query-slice staging by waves 0-3 (32 rows x 8 16-B chunks = 256 lanes): thread -> (row sr,
+  // chunk sc) of Q, dO and O; indices from an opaque copy of tid per slice, as in the 4-wave kernel
+  const bool stager = wave < 4;
+  struct SRegs { bf16x8 q, o, d; float l; };
+  auto load_slice = [&](int t, SRegs& x, int tid_t) {
+    const int sr = tid_t >> 3, sc = tid_t & 7;
+    const int q = 32 * t + sr;
+    x.q = *reinterpret_cast<const bf16x8*>(base + (size_t)q * ld + h * D + sc * 8);
+    x.o = *reinterpret_cast<const bf16x8*>(out + obase + (size_t)q * (H * D) + sc * 8);
+    x.d = *reinterpret_cast<const bf16x8*>(dout + obase + (size_t)q * (H * D) + sc * 8);
+    x.l = lse_bh[q];
+  };
+  auto store_slice = [&](int buf, int t, const SRegs& x, int tid_t) {
+    const int sr = tid_t >> 3, sc = tid_t & 7;
+    *reinterpret_cast<bf16x8*>(Qimg + buf * 32 * D + swz(sr, sc * 8)) = x.q;
+    *reinterpret_cast<bf16x8*>(Oimg + buf * 32 * D + swz(sr, sc * 8)) = x.d;
+    float dl = 0.f;  // delta = rowsum(dO * O) over the row's 8 chunks (8 consecutive lanes)
+#pragma unroll
+    for (int j = 0; j < 8; ++j) dl = fmaf((float)x.d[j], (float)x.o[j], dl);
+    dl += dppf<0xB1>(dl);   // quad_perm [1,0,3,2]
+    dl += dppf<0x4E>(dl);   // quad_perm [2,3,0,1]: quad sum in every lane
+    dl += dppf<0x141>(dl);  // row_half_mirror: + the other quad of the 8-lane row group
+    if (sc == 0) {
+      const float l2 = x.l * LOG2E, sq = slope2 * (float)(32 * t + sr);
+      float* R = rc + buf * 128 + sr;
+      R[0] = (-l2 - sq) * invc;  // query after the key block
+      R[32] = (-l2 + sq) * invc; // query before
+      R[64] = -l2 * invc;        // diagonal block
+      R[96] = -dl;
+    }
+  };
+
+  f32x16 dk[KB][2], dv[KB][2];
+  if (DB)
+    for (int i = tid; i < 2 * S; i += 512) sigl[i] = 0.f;
+#pragma unroll
+  for (int kb = 0; kb < KB; ++kb) {
+#pragma unroll
+    for (int i = 0; i < 16; ++i) { dk[kb][0][i] = dk[kb][1][i] = dv[kb][0][i] = dv[kb][1][i] = 0.f; }
+  }
+  const int dth = wave & 1, kq = wave >> 1;  // phase-2 role: 32-d half, key quarter
+  // LDS byte addresses. The slice loop has some forty distinct per-lane addresses; left to the
+  // compiler they are either all hoisted (and spill) or all recomputed through swz() (more
+  // integer VALU than softmax). Six per-lane bases are kept instead, and every other address is
+  // a base plus a wave-uniform term, XOR a constant, plus an immediate:
+  //  swz(r, c ^ 8x) = swz(r, c) ^ 8x for chunk bits x (the swizzle is an XOR on the chunk), and
+  //  rows r + 8, r < 8, flip key bit 0: swz(r + 8, c) = (swz(r, c) ^ 8) + 8 * D;
+  // the uniform terms are multiples of the 128-B (dS^T: 64-B) rows, so they commute with the XORs.
+  // The bases are passed through empty asm in the loop so that nothing derived from them is
+  // loop-invariant.
+  const int tq0 = 4 * (g16 >> 1) + (i16 >> 2), tc0 = 16 * (g16 & 1) + 4 * (i16 & 3);
+  unsigned a_f = 2 * swz(kl, 8 * hh);   // fragment rows of Q / dO / K: step s is ^ 32s
+  unsigned a_t = 2 * swz(tq0, tc0);     // transposed reads: rows + 8 are ^ 16, d + 32 is ^ 64
+  unsigned a_d = lds_addr(dST + wave * KPW * 32) + 2 * (kl * 32 + 4 * (hh ^ ((kl >> 1) & 7)));  // dS^T write, group g: ^ 16g
+  unsigned a_s = lds_addr(dST + kq * (S / 4) * 32) + 2 * (tq0 * 32 + 4 * ((tc0 >> 2) ^ ((tq0 >> 1) & 7)));  // dS^T read
+  unsigned a_g = lds_addr(sigl + hh * S + wave * KPW + kl);
+  unsigned v_off = (unsigned)(wave * KPW + kl) * (unsigned)ld + 8 * hh;  // V row of the lane
+  const unsigned s_K = lds_addr(Kimg + wave * KPW * D), s_Kq = lds_addr(Kimg + kq * (S / 4) * D);
+  const unsigned s_red = lds_addr(red + dth * (4 * 3 * 256));  // dQ partials: [src quarter][3][256]
+  if (stager) {
+    SRegs x;
+    load_slice(0, x, tid);
+    store_slice(0, 0, x, tid);
+  }
+  __syncthreads();
+  BWD8_STAMP(16, 1);
+
+  for (int t = 0; t < NS; ++t) {
+    BWD8_STAMP(t, 0);
+    const int buf = t & 1;
+    int tid_t = tid;  // opaque per slice: lane-derived values are recomputed, not kept live
+    asm volatile("" : "+v"(tid_t));
+    unsigned padm_t = padm;
+    asm volatile("" : "+v"(padm_t));
+    SRegs nx;  // next slice's Q / O / dO / LSE (waves 0-3): loaded once the last block's scores
+               // are packed, stored to LDS after phase 2
+    const unsigned s_Q = lds_addr(Qimg + buf * 32 * D);  // dO image: + O_OFF
+    constexpr unsigned O_OFF = 2 * 32 * D * 2;
+    const unsigned s_rc = lds_addr(rc + buf * 128);
+    const int qb = 32 * t;
+    // ---- phase 1: the wave's key blocks one after the other
+#pragma unroll
+    for (int kb = 0; kb < KB; ++kb) {
+      __builtin_amdgcn_sched_barrier(0);
+      asm volatile("" : "+v"(a_f), "+v"(a_g), "+v"(v_off));
+      const int hh_b = (tid_t >> 5) & 1;
+      const int kbase = wave * KPW + 32 * kb;  // uniform
+      const bool after = qb > kbase, before = qb < kbase;
+      const int sel = after ? 0 : (before ? 1 : 2);
+      const unsigned a_rc = s_rc + sel * 128 + 16 * hh_b, a_dl = s_rc + 3 * 128 + 16 * hh_b;
+      f32x16 sa, pa;
+#pragma unroll
+      for (int g4 = 0; g4 < 4; ++g4) {
+        const f32x4 l4 = lds_ld<f32x4>(a_rc + 32 * g4);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) sa[4 * g4 + e] = l4[e];
+      }
+#pragma unroll
+      for (int g4 = 0; g4 < 4; ++g4) {  // -delta of the slice's rows: the dP' initial accumulator
+        const f32x4 d4 = lds_ld<f32x4>(a_dl + 32 * g4);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) pa[4 * g4 + e] = d4[e];
+      }
+      const unsigned a_q = a_f + s_Q, a_k = a_f + s_K;
+#pragma unroll
+      for (int s = 0; s < 4; ++s) {
+        const bf16x8 of = lds_ld<bf16x8>((a_q ^ (32 * s)) + O_OFF);
+        const bf16x8 qf = lds_ld<bf16x8>(a_q ^ (32 * s));
+        const bf16x8 kr = lds_ld<bf16x8>((a_k ^ (32 * s)) + kb * 32 * D * 2);
+        pa = mfma(of, vf[s], pa);  // dP - delta
+        sa = mfma(qf, kr, sa);     // (S - LSE2 -+ slope2 q) / c   [q][key]
+      }
+      if (KB > 1) {
+#pragma unroll
+        for (int s = 0; s < 4; ++s)
+          vf[s] = *reinterpret_cast<const bf16x8*>(vbase + (v_off + ((kb + 1) % KB) * 32 * ld) + 16 * s);
+      }
+      const int kl_b = tid_t & 31;
+      const float kbias = ((padm_t >> kb) & 1) ? PAD_BIAS * LOG2E : 0.f;
+      const float U = (after || before) ? fmaf(after ? slope2 : -slope2, (float)(kbase + kl_b), kbias) : kbias;
+      if (!after && !before) {
+        // diagonal block (qb == kbase): q - k at register offset 0 is 4hh - kl, opaque to the
+        // optimizer (it would keep the 16 loop-invariant |q - k| in registers)
+        float lq = (float)(4 * hh_b - kl_b);
+        asm volatile("" : "+v"(lq));
+#pragma unroll
+        for (int r = 0; r < 16; ++r) sa[r] = fmaf(-sl_t, fabsf(lq + (float)aoff(r)), sa[r]);
+      }
+      const float sold = DB ? lds_ld<float>(a_g + kb * 32 * 4) : 0.f;
+      bf16x8 pb[2], sb[2];
+      float ssum = 0.f;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const float pr = ex2(fmaf(sa[r], c, U));
+        const float ds = pr * pa[r];
+        pb[r >> 3][r & 7] = (bf16)pr;
+        sb[r >> 3][r & 7] = (bf16)ds;
+        if (DB) ssum += ds;
+      }
+      if (DB) lds_st<float>(a_g + kb * 32 * 4, sold + ssum);
+      if (kb == KB - 1 && t + 1 < NS && stager) load_slice(t + 1, nx, tid_t);
+      // dS^T image of the block: register group g holds q = 8g + 4hh + 0..3 of key kl (chunk
+      // swizzle as in the 4-wave kernel)
+      asm volatile("" : "+v"(a_d), "+v"(a_t));
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        const bf16x8& src = sb[g >> 1];
+        const bf16x4 v = {src[4 * (g & 1)], src[4 * (g & 1) + 1], src[4 * (g & 1) + 2], src[4 * (g & 1) + 3]};
+        lds_st<bf16x4>((a_d ^ (16 * g)) + kb * 32 * 32 * 2, v);
+      }
+      // dV^T += dO^T P, dK^T += Q^T dS: pair j = (s2, dt), two pairs of transposed reads in flight
+      const unsigned a_tq = a_t + s_Q;
+      auto tr_pair = [&](unsigned img_off, int j) {  // A operand (dO^T or Q^T) of pair j = (s2, dt)
+        const unsigned a0 = (a_tq ^ (64 * (j & 1))) + img_off + (j >> 1) * 16 * D * 2;
+        const unsigned a1 = (a_tq ^ (64 * (j & 1) + 16)) + img_off + (j >> 1) * 16 * D * 2 + 8 * D * 2;
+        return cat(tr_read_a(a0), tr_read_a(a1));
+      };
+      bf16x8 ao[2], aq[2];
+      ao[0] = tr_pair(O_OFF, 0); aq[0] = tr_pair(0, 0);
+      ao[1] = tr_pair(O_OFF, 1); aq[1] = tr_pair(0, 1);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        mfma_acc(dv[kb][j & 1], ao[j & 1], pb[j >> 1]);
+        mfma_acc(dk[kb][j & 1], aq[j & 1], sb[j >> 1]);
+        if (j < 2) { ao[j & 1] = tr_pair(O_OFF, j + 2); aq[j & 1] = tr_pair(0, j + 2); }
+      }
+    }
+    BWD8_STAMP(t, 1);
+    __syncthreads();
+    BWD8_STAMP(t, 2);
+    // ---- phase 2: dQ^T[32 dth + d][q] over keys [kq*S/4, (kq+1)*S/4)
+    f32x16 dq;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) dq[i] = 0.f;
+    asm volatile("" : "+v"(a_t), "+v"(a_s));
+    {
+      // K^T rows 16ks + tq0 (and + 8) at d = 32 dth + tc0; dS^T rows likewise at q = tc0
+      const unsigned a_k0 = (a_t ^ (64 * dth)) + s_Kq;
+      constexpr int PF = KS2 < 4 ? KS2 : 4;
+      bf16x8 ra[PF], rb[PF];
+      auto rd = [&](int ks, bf16x8& a, bf16x8& bb) {
+        a = cat(tr_read_a(a_k0 + ks * 16 * D * 2), tr_read_a((a_k0 ^ 16) + ks * 16 * D * 2 + 8 * D * 2));
+        bb = cat(tr_read_a(a_s + ks * 16 * 32 * 2), tr_read_a((a_s ^ 32) + ks * 16 * 32 * 2 + 8 * 32 * 2));
+      };
+#pragma unroll
+      for (int ks = 0; ks < PF; ++ks) rd(ks, ra[ks], rb[ks]);
+#pragma unroll
+      for (int ks = 0; ks < KS2; ++ks) {
+        dq = mfma(ra[ks % PF], rb[ks % PF], dq);
+        if (ks + PF < KS2) rd(ks + PF, ra[ks % PF], rb[ks % PF]);
+      }
+    }
+    // key-quarter partials: the wave of quarter kq finishes register group g = kq and passes its
+    // other three groups through LDS (slot g - (g > kq) of its source quarter)
+    const unsigned a_red = s_red + 16 * (tid_t & 63);
+#pragma unroll
+    for (int g = 0; g < 4; ++g)
+      if (g != kq)
+        lds_st<f32x4>(a_red + (kq * 3 + (g > kq ? g - 1 : g)) * 1024,
+                      f32x4{dq[4 * g], dq[4 * g + 1], dq[4 * g + 2], dq[4 * g + 3]});
+    BWD8_STAMP(t, 3);
+    if (t + 1 < NS && stager) store_slice(buf ^ 1, t + 1, nx, tid_t);
+    __syncthreads();
+    BWD8_STAMP(t, 4);
+    {
+      bf16* row = dqkv + (size_t)b * S * ld + h * D + 32 * dth +
+                  ((unsigned)(qb + (tid_t & 31)) * (unsigned)ld + 4 * ((tid_t >> 5) & 1));
+#pragma unroll
+      for (int g = 0; g < 4; ++g)
+        if (g == kq) {
+          f32x4 p[4];  // quarter partials of group g, summed (q0 + q1) + (q2 + q3) by every wave
+#pragma unroll
+          for (int ks = 0; ks < 4; ++ks)
+            p[ks] = ks == g ? f32x4{dq[4 * g], dq[4 * g + 1], dq[4 * g + 2], dq[4 * g + 3]}
+                            : lds_ld<f32x4>(a_red + (ks * 3 + (g > ks ? g - 1 : g)) * 1024);
+          bf16x4 o;
+#pragma unroll
+          for (int e = 0; e < 4; ++e) o[e] = (bf16)(((p[0][e] + p[1][e]) + (p[2][e] + p[3][e])) * scale);
+          *reinterpret_cast<bf16x4*>(row + 8 * g) = o;
+        }
+    }
+    BWD8_STAMP(t, 5);
+  }
+  BWD8_STAMP(16, 2);
+
+  // ---- dK, dV rows of this wave's keys
+#pragma unroll
+  for (int kb = 0; kb < KB; ++kb)
+#pragma unroll
+    for (int dt = 0; dt < 2; ++dt) acc_fence(dk[kb][dt], dv[kb][dt]);
+  // A lane holds 4 consecutive d of its key per register group: stored directly, every store
+  // instruction would touch 64 rows with 8 B each (measured: 10-20k cycles of the workgroup's
+  // 163k went into these stores). Each [32 keys][64 d] bf16 tile goes through a wave-private
+  // 4-KiB LDS tile instead (the Q / dO / dS^T images are dead after the loop's last barrier; LDS
+  // is in order within a wave, so no barrier), 16-B chunks XOR (key & 7), and leaves as whole
+  // 128-B rows, 8 lanes per row.
+  static_assert(8 * 4096 <= 4 * 32 * D * 2 + S * 32 * 2, "store tiles fit the dead images");
+  {
+    const unsigned a_w = lds_addr(Qimg) + wave * 4096 + kl * 128 + ((kl & 7) << 4) + 8 * hh;
+    const int srow = lane >> 3, sch = lane & 7;
+    const unsigned a_r = lds_addr(Qimg) + wave * 4096 + srow * 128 + ((sch ^ srow) << 4);
+    bf16* grow = dqkv + ((size_t)b * S + wave * KPW + srow) * ld + h * D + 8 * sch;
+#pragma unroll
+    for (int kb = 0; kb < KB; ++kb)
+#pragma unroll
+      for (int ts = 0; ts < 2; ++ts) {  // dK (scaled), dV
+#pragma unroll
+        for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+          for (int g = 0; g < 4; ++g) {
+            bf16x4 v;
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+              v[e] = ts == 0 ? (bf16)(dk[kb][dt][4 * g + e] * scale) : (bf16)dv[kb][dt][4 * g + e];
+            lds_st<bf16x4>(a_w ^ ((4 * dt + g) << 4), v);  // chunk (4dt + g) ^ (kl & 7)
+          }
+#pragma unroll
+        for (int i = 0; i < 4; ++i)  // rows srow + 8i: (row & 7) = srow
+          *reinterpret_cast<bf16x8*>(grow + (size_t)(32 * kb + 8 * i) * ld + (1 + ts) * H * D) =
+              lds_ld<bf16x8>(a_r + i * 8 * 128);
+      }
+  }
+  BWD8_STAMP(16, 3);
+  if (DB) {
+    // column sums per 128 keys. Waves 2j, 2j+1 hold the keys of wave j of the 4-wave kernel and
+    // repeat its summation order: per (d, key lane) the even wave's blocks then the odd wave's,
+    // passed through the pair's [64 d][key] staging image, then the odd wave's row sums over the
+    // 32 key lanes; every wave reaches every barrier
+#pragma unroll
+    for (int kb = 0; kb < KB; ++kb)
+#pragma unroll
+      for (int dt = 0; dt < 2; ++dt) asm volatile("" : "+a"(dk[kb][dt]), "+a"(dv[kb][dt]));
+    __syncthreads();  // the last slice's dQ partials have been read; images and red are dead
+    int lane_e = lane;
+    asm volatile("" : "+v"(lane_e));
+    const int kl_e = lane_e & 31, hh_e = lane_e >> 5;
+    const int pair = wave >> 1;
+    const bool odd = (wave & 1) != 0;
+    float* cs = sigl + 2 * S;  // [pair][dQ, dK, dV][64]
+    float* st = reinterpret_cast<float*>(Qimg) + pair * 64 * CS_LD;
+    auto rowsum = [&](float* dst) {
+      f32x4 a = *reinterpret_cast<const f32x4*>(st + lane_e * CS_LD);
+#pragma unroll
+      for (int k = 4; k < 32; k += 4) {
+        const f32x4 v = *reinterpret_cast<const f32x4*>(st + lane_e * CS_LD + k);
+        a[0] += v[0]; a[1] += v[1]; a[2] += v[2]; a[3] += v[3];
+      }
+      *dst = (a[0] + a[1]) + (a[2] + a[3]);
+    };
+    // dQ part: sum_key K[key][d] * sigma[key] over this lane's half of d
+    auto dq_part = [&](bool first) {
+      float sgm[KB];
+#pragma unroll
+      for (int kb = 0; kb < KB; ++kb) {
+        const int key = wave * KPW + 32 * kb + kl_e;
+        sgm[kb] = sigl[key] + sigl[S + key];
+      }
+#pragma unroll
+      for (int cc = 0; cc < 4; ++cc) {
+        float a8[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) a8[e] = first ? 0.f : st[(32 * hh_e + 8 * cc + e) * CS_LD + kl_e];
+#pragma unroll
+        for (int kb = 0; kb < KB; ++kb) {
+          const int r = wave * KPW + 32 * kb + kl_e;
+          const bf16x8 v = *reinterpret_cast<const bf16x8*>(Kimg + r * D + (((4 * hh_e + cc) ^ swz_key(r)) << 3));
+#pragma unroll
+          for (int e = 0; e < 8; ++e) a8[e] = fmaf((float)v[e], sgm[kb], a8[e]);
+        }
+#pragma unroll
+        for (int e = 0; e < 8; ++e) st[(32 * hh_e + 8 * cc + e) * CS_LD + kl_e] = first ? a8[e] : a8[e] * scale;
+      }
+    };
+    if (!odd) dq_part(true);
+    __syncthreads();
+    if (odd) {
+      dq_part(false);
+      rowsum(cs + (pair * 3) * 64 + lane_e);
+    }
+    __syncthreads();
+#pragma unroll
+    for (int ts = 0; ts < 2; ++ts) {  // dK (scaled), dV
+      auto acc_part = [&](bool first) {
+#pragma unroll
+        for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+          for (int r = 0; r < 16; ++r) {
+            float* p = st + (32 * dt + aoff(r) + 4 * hh_e) * CS_LD + kl_e;
+            float sum = first ? 0.f : *p;
+#pragma unroll
+            for (int kb = 0; kb < KB; ++kb) sum += ts == 0 ? dk[kb][dt][r] : dv[kb][dt][r];
+            *p = (first || ts == 1) ? sum : sum * scale;
+          }
+      };
+      if (!odd) acc_part(true);
+      __syncthreads();
+      if (odd) {
+        acc_part(false);
+        rowsum(cs + (pair * 3 + 1 + ts) * 64 + lane_e);
+      }
+      __syncthreads();
+    }
+    for (int i = tid; i < 2 * KB * 192; i += 512) {
+      const int j = i / 192, ts = (i >> 6) % 3, d = i & 63;
+      float sum = 0.f;
+#pragma unroll
+      for (int w = 0; w < 2 / KB; ++w) sum += cs[((j * 2 / KB + w) * 3 + ts) * 64 + d];
+      dbias_part[((size_t)b * 2 * KB + j) * ld + ts * H * D + h * D + d] = sum;
+    }
+  }
+  BWD8_STAMP(16, 4);
 }
 
 // ----------------------------------------------------------------------------- fp32 path
@@ -2144,11 +2617,41 @@ static void launch_bwd3(const void* qkv, const void* out, const void* dout, cons
   }
 }
 
-extern "C" int dna_attn_bwd_ex(const void* qkv, const void* out, const void* dout,
-                               const float* lse, const uint8_t* key_valid, const float* slopes,
-                               int batch, int seqlen, int heads, int head_dim, int dtype,
-                               float softmax_scale, void* dqkv, float* delta_ws, float* dbias_part,
-                               void* stream) {
+template <int KB>
+static void launch_bwd3w8(const void* qkv, const void* out, const void* dout, const float* lse,
+                          const uint8_t* key_valid, const float* slopes, int batch, int heads,
+                          float c, float scale, void* dqkv, float* dbias_part, hipStream_t s) {
+  static const bool attr = [] {
+    const void* ks[] = {(const void*)bwd3w8_bf16_kernel<KB, false>, (const void*)bwd3w8_bf16_kernel<KB, true>};
+    for (const void* k : ks)
+      (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bwd8_lds<KB>());
+    return true;
+  }();
+  (void)attr;
+  const dim3 grid(batch * heads);
+  const size_t lds = bwd8_lds<KB>();
+  auto args = [&](auto kern, float* part) {
+    hipLaunchKernelGGL(kern, grid, dim3(512), lds, s, (const bf16*)qkv, (const bf16*)out,
+                       (const bf16*)dout, lse, key_valid, slopes, heads, c, scale, (bf16*)dqkv, part);
+  };
+  if (!dbias_part) args(bwd3w8_bf16_kernel<KB, false>, nullptr);
+  else args(bwd3w8_bf16_kernel<KB, true>, dbias_part);
+}
+
+// waves per workgroup of the fused backward at S = 256 / 512: DNA_ATTN_BWD3_NW = 4 or 8, read once.
+// Unset: 8 at S = 512 (attn_bwd 1.91 -> 1.71 ms per launch in the DNABERT-2 bench, b = 512,
+// interleaved A/B in profiles/r07/ab_attn_bwd_8wave.txt), 4 at S = 256 (not measured in a
+// training step)
+static int bwd3_nw_default(int seqlen) {
+  static const int nw = getenv("DNA_ATTN_BWD3_NW") ? atoi(getenv("DNA_ATTN_BWD3_NW")) : 0;
+  return nw ? nw : (seqlen == 512 ? 8 : 4);
+}
+
+// nw: 0 = the DNA_ATTN_BWD / DNA_ATTN_BWD3_NW defaults, 4 or 8 = the fused kernel with that many waves
+static int attn_bwd_impl(const void* qkv, const void* out, const void* dout, const float* lse,
+                         const uint8_t* key_valid, const float* slopes, int batch, int seqlen,
+                         int heads, int head_dim, int dtype, float softmax_scale, void* dqkv,
+                         float* delta_ws, float* dbias_part, int nw, void* stream) {
   int st = check_common(qkv, slopes, batch, seqlen, heads, head_dim, dtype, "dna_attn_bwd");
   if (st) return st;
   DNA_CHECK_ARG(out && dout && lse && dqkv && delta_ws, "dna_attn_bwd: null pointer");
@@ -2157,11 +2660,17 @@ extern "C" int dna_attn_bwd_ex(const void* qkv, const void* out, const void* dou
   const int nd = (rows * heads + 255) / 256;
   // DNA_ATTN_BWD: 3 (default) fused one-workgroup-per-(batch, head) kernel where S is 128, 256
   // or 512, else the v2 pair; 2 forces the v2 pair, 1 the v1 pair (benchmarks / A/B)
-  static const int bwd_ver = getenv("DNA_ATTN_BWD") ? atoi(getenv("DNA_ATTN_BWD")) : 3;
+  static const int bwd_env = getenv("DNA_ATTN_BWD") ? atoi(getenv("DNA_ATTN_BWD")) : 3;
+  const int bwd_ver = nw ? 3 : bwd_env;
   const bool bwd_v1 = bwd_ver == 1;
   if (dtype == DNA_BF16 && bwd_ver == 3 && (seqlen == 128 || seqlen == 256 || seqlen == 512)) {
     const float c = softmax_scale * LOG2E;
-    if (seqlen == 512)
+    const bool w8 = (nw ? nw : bwd3_nw_default(seqlen)) == 8 && seqlen != 128;
+    if (w8 && seqlen == 512)
+      launch_bwd3w8<2>(qkv, out, dout, lse, key_valid, slopes, batch, heads, c, softmax_scale, dqkv, dbias_part, s);
+    else if (w8)
+      launch_bwd3w8<1>(qkv, out, dout, lse, key_valid, slopes, batch, heads, c, softmax_scale, dqkv, dbias_part, s);
+    else if (seqlen == 512)
       launch_bwd3<4>(qkv, out, dout, lse, key_valid, slopes, batch, heads, c, softmax_scale, dqkv, dbias_part, s);
     else if (seqlen == 256)
       launch_bwd3<2>(qkv, out, dout, lse, key_valid, slopes, batch, heads, c, softmax_scale, dqkv, dbias_part, s);
@@ -2218,6 +2727,29 @@ extern "C" int dna_attn_bwd_ex(const void* qkv, const void* out, const void* dou
   }
   DNA_LAUNCH_CHECK("dna_attn_bwd");
   return DNA_OK;
+}
+
+extern "C" int dna_attn_bwd_ex(const void* qkv, const void* out, const void* dout,
+                               const float* lse, const uint8_t* key_valid, const float* slopes,
+                               int batch, int seqlen, int heads, int head_dim, int dtype,
+                               float softmax_scale, void* dqkv, float* delta_ws, float* dbias_part,
+                               void* stream) {
+  return attn_bwd_impl(qkv, out, dout, lse, key_valid, slopes, batch, seqlen, heads, head_dim, dtype,
+                       softmax_scale, dqkv, delta_ws, dbias_part, 0, stream);
+}
+
+extern "C" int dna_attn_bwd_var(const void* qkv, const void* out, const void* dout,
+                                const float* lse, const uint8_t* key_valid, const float* slopes,
+                                int batch, int seqlen, int heads, int head_dim, int dtype,
+                                float softmax_scale, void* dqkv, float* delta_ws, float* dbias_part,
+                                int nw, void* stream) {
+  DNA_CHECK_ARG(nw == 4 || nw == 8, "dna_attn_bwd_var: nw %d (4 or 8)", nw);
+  if (dtype != DNA_BF16 || !(seqlen == 512 || seqlen == 256 || (nw == 4 && seqlen == 128))) {
+    set_error("dna_attn_bwd_var: no %d-wave fused backward for dtype %d, seqlen %d", nw, dtype, seqlen);
+    return DNA_ERR_UNSUPPORTED;
+  }
+  return attn_bwd_impl(qkv, out, dout, lse, key_valid, slopes, batch, seqlen, heads, head_dim, dtype,
+                       softmax_scale, dqkv, delta_ws, dbias_part, nw, stream);
 }
 
 extern "C" int dna_attn_bwd(const void* qkv, const void* out, const void* dout, const float* lse,

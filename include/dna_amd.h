@@ -96,6 +96,15 @@ int dna_attn_bwd_ex(const void* qkv, const void* out, const void* dout, const fl
                     const uint8_t* key_valid, const float* slopes, int batch, int seqlen, int heads,
                     int head_dim, int dtype, float softmax_scale, void* dqkv, float* delta_ws,
                     float* dbias_part, void* stream);
+/* dna_attn_bwd_ex with the fused one-workgroup-per-(batch, head) bf16 kernel chosen by its
+ * waves per workgroup, nw = 4 or 8, whatever DNA_ATTN_BWD / DNA_ATTN_BWD3_NW say (tests and A/B
+ * runs compare both in one process). nw = 4: seqlen 128, 256 or 512; nw = 8: seqlen 256 or 512;
+ * anything else is DNA_ERR_UNSUPPORTED. dK, dV and dbias_part are bit-identical between the
+ * two; dQ sums its key partials in a different (fixed) order. */
+int dna_attn_bwd_var(const void* qkv, const void* out, const void* dout, const float* lse,
+                     const uint8_t* key_valid, const float* slopes, int batch, int seqlen, int heads,
+                     int head_dim, int dtype, float softmax_scale, void* dqkv, float* delta_ws,
+                     float* dbias_part, int nw, void* stream);
 int dna_attn_dbias_part_rows(int batch, int seqlen);
 
 /* ------------------------------------------------------------------ fused (bias, act, dropout, residual) + LayerNorm
