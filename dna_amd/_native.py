@@ -17,6 +17,7 @@ HEADER = os.path.join(os.path.dirname(_HERE), "include", "dna_amd.h")
 
 F32, BF16, F16 = 0, 1, 2
 ACT_NONE, ACT_GELU = 0, 1
+CLS_REGRESSION, CLS_SINGLE_LABEL, CLS_MULTI_LABEL = 0, 1, 2
 
 _vp, _i, _u64, _f, _sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_uint64, ctypes.c_float, ctypes.c_size_t
 _i64 = ctypes.c_int64
@@ -113,6 +114,13 @@ _SIGS = {
     "dna_selective_scan_bwd": (_i, [_vp] * 8 + [_i] * 6 + [_vp] * 11),
     "dna_xent_fwd": (_i, [_vp, _i, _vp, _i, _i, _vp, _vp, _vp]),
     "dna_xent_bwd": (_i, [_vp, _i, _vp, _vp, _vp, _f, _i, _i, _vp, _vp]),
+    "dna_cls_head_fwd_workspace": (_sz, [_i, _i, _i]),
+    "dna_cls_head_fwd": (_i, [_vp, _i, _i64, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _u64, _u64, _vp,
+                              _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "dna_cls_loss": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "dna_cls_head_bwd_workspace": (_sz, [_i, _i, _i]),
+    "dna_cls_head_bwd": (_i, [_vp, _vp, _vp, _i, _i64, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _u64,
+                              _u64, _vp, _vp, _vp, _vp, _vp, _i, _vp, _sz, _vp]),
     "dna_sumsq_workspace": (_sz, [_sz]),
     "dna_sumsq": (_i, [_vp, _sz, _vp, _vp, _sz, _vp]),
     "dna_adamw_step": (_i, [_vp, _vp, _vp, _vp, _vp, _sz, _f, _f, _f, _f, _f, _i, _vp, _f, _f,

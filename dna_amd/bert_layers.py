@@ -39,6 +39,19 @@ except Exception:  # pragma: no cover - transformers is part of the image; keep 
         def __getitem__(self, i):
             return (self.loss, self.logits)[i]
 
+try:  # BertForSequenceClassification returns transformers' SequenceClassifierOutput (:1004-1009)
+    from transformers.modeling_outputs import SequenceClassifierOutput
+except Exception:  # pragma: no cover
+    @dataclass
+    class SequenceClassifierOutput:
+        loss: Optional[torch.Tensor] = None
+        logits: Optional[torch.Tensor] = None
+        hidden_states: Optional[object] = None
+        attentions: Optional[object] = None
+
+        def __getitem__(self, i):
+            return tuple(v for v in (self.loss, self.logits) if v is not None)[i]
+
 PAD_TOKEN_ID = 3  # DNABERT-2 tokenizer [PAD] (tokenizer.json added_tokens)
 
 
@@ -107,14 +120,210 @@ class BertEncoder(nn.Module):
                                           dtype=torch.float32), persistent=False)
 
 
-class BertModel(nn.Module):
-    def __init__(self, config, add_pooling_layer=False):
+class BertPooler(nn.Module):
+    """tanh(dense(hidden[:, 0])) (reference bert_layers.py:495-510); runs inside the fused head
+    kernel (DF.ClsHead / DF.pooler), which reads dense.weight / dense.bias in fp32."""
+
+    def __init__(self, config):
         super().__init__()
-        if add_pooling_layer:
-            raise NotImplementedError("pooler is outside the MLM hot path")
+        self.dense = nn.Linear(config.hidden_size, config.hidden_size)
+        self.activation = nn.Tanh()
+
+
+def _init_bert_weights(module, std):
+    """BertPreTrainedModel._init_weights semantics: N(0, initializer_range) for Linear and
+    Embedding weights, zero biases, LayerNorm (1, 0), zero padding_idx row."""
+    for m in module.modules():
+        if isinstance(m, nn.Linear):
+            nn.init.normal_(m.weight, mean=0.0, std=std)
+            if m.bias is not None:
+                nn.init.zeros_(m.bias)
+        elif isinstance(m, nn.Embedding):
+            nn.init.normal_(m.weight, mean=0.0, std=std)
+            if m.padding_idx is not None:
+                with torch.no_grad():
+                    m.weight[m.padding_idx].zero_()
+        elif isinstance(m, nn.LayerNorm):
+            nn.init.ones_(m.weight)
+            nn.init.zeros_(m.bias)
+
+
+def _tag_projections(root, skip=()):
+    """Projection weights keep a W^T copy for the data gradient dx = dy . W^T^T, where the MFMA
+    kernel wants the reduction (out features) % 64 and the output (in features) % 8, as
+    dna_transpose_bf16 does; other shapes keep the library dgrad. `skip`: Linear modules whose
+    weights only the head kernel reads (pooler.dense, classifier)."""
+    for m in root.modules():
+        if (isinstance(m, nn.Linear) and m.out_features % 64 == 0 and m.in_features % 8 == 0
+                and not any(m is q for q in skip)):
+            m.weight._dna_transpose = True
+
+
+class _HipEncoder:
+    """Mixin of the models that run the encoder on the HIP kernels: compute precision, the
+    dropout stream, the compute-dtype weight views (FlatParams) and the encoder loop itself.
+    `self._bert_model()` is the BertModel holding embeddings and encoder."""
+
+    def _init_hip_encoder(self, precision):
+        assert precision in ("bf16", "fp32")
+        self.precision = precision
+        self.dropout_rng = DF.DropoutRNG()
+        self._lp_provider = None  # set by dna_amd.flat.FlatParams for a persistent bf16 copy
+        self._lpt_provider = None  # ... and for the transposed bf16 projection weights
+
+    def _bert_model(self):
+        return self.bert
+
+    def set_precision(self, precision: str):
+        assert precision in ("bf16", "fp32")
+        self.precision = precision
+        return self
+
+    @property
+    def compute_dtype(self):
+        return torch.bfloat16 if self.precision == "bf16" else torch.float32
+
+    def _lp(self, p: torch.Tensor) -> torch.Tensor:
+        """Compute-dtype view of master weight `p` (persistent shadow if a FlatParams owns it)."""
+        if self.precision == "fp32":
+            return p
+        if self._lp_provider is not None:
+            return self._lp_provider(p)
+        return p.detach().to(torch.bfloat16)
+
+    def _lp_t(self, p: torch.Tensor):
+        """Transposed bf16 copy of projection weight `p` (None: the data gradient falls back)."""
+        if self.precision == "fp32" or self._lpt_provider is None:
+            return None
+        return self._lpt_provider(p)
+
+    def _linear(self, x, w, b=None, geglu=None):
+        return DF.linear(x, w, self._lp(w), b, w_lpt=self._lp_t(w), geglu=geglu)
+
+    def _check_inputs(self, input_ids, token_type_ids, attention_mask):
+        if input_ids is None:
+            raise ValueError("Must specify input_ids (inputs_embeds is not supported)")
+        if token_type_ids is not None and bool((token_type_ids != 0).any()):
+            raise NotImplementedError("token_type_ids other than 0 (the MLM path never sets them)")
+        if attention_mask is not None:
+            if not torch.equal(attention_mask.bool(), input_ids != self.config.pad_token_id_mask):
+                raise NotImplementedError("attention_mask must equal input_ids != [PAD]")
+
+    def encode(self, input_ids: torch.Tensor, last_rows: Optional[torch.Tensor] = None):
+        """Embeddings + encoder -> (x fp32, x compute dtype) of the last layer, rows flattened
+        over (b, s). last_rows (flattened row indices): the last layer's output projection, MLP
+        and LayerNorms run on those rows only and the result holds just them (reference
+        :469-488 `subset_mask`). bf16 mode with S % 64 != 0 (the attention kernel's tile): the ids
+        are padded with [PAD] to the next multiple of 64 and the outputs sliced back -- pad keys
+        are excluded in the kernel and ALiBi depends on i - j only, so valid rows are unchanged."""
+        cfg = self.config
+        bert = self._bert_model()
+        b, S0 = input_ids.shape
+        bf16 = self.precision == "bf16"
+        S = S0
+        if bf16 and S0 % 64:
+            S = (S0 + 63) // 64 * 64
+            input_ids = torch.nn.functional.pad(input_ids, (0, S - S0), value=cfg.pad_token_id_mask)
+            if last_rows is not None:
+                last_rows = torch.div(last_rows, S0, rounding_mode="floor") * S + last_rows % S0
+        T = b * S
+        H = cfg.num_attention_heads
+        train = self.training
+        rng = self.dropout_rng
+        p_hidden = cfg.hidden_dropout_prob if train else 0.0
+        if cfg.attention_probs_dropout_prob and train:
+            raise NotImplementedError("attention-probability dropout (reference default 0.0)")
+        eps = cfg.layer_norm_eps
+        ids = input_ids.reshape(-1)
+        key_valid = (ids != cfg.pad_token_id_mask).to(torch.uint8)
+
+        emb = bert.embeddings
+        seed, off = rng.take(T * cfg.hidden_size) if p_hidden else (0, 0)
+        x32, xb = DF.EmbeddingLN.apply(ids, emb.word_embeddings.weight,
+                                       emb.token_type_embeddings.weight, emb.LayerNorm.weight,
+                                       emb.LayerNorm.bias, eps, p_hidden, seed, off, True, bf16)
+        xin = xb if bf16 else x32
+        slopes = bert.encoder.alibi_slopes
+        L = len(bert.encoder.layer)
+        for i, layer in enumerate(bert.encoder.layer):
+            att = layer.attention
+            qkv = self._linear(xin, att.self.Wqkv.weight, att.self.Wqkv.bias)
+            ctx = DF.alibi_attention(qkv, key_valid, slopes, b, S, H,
+                                     bias_grad=att.self.Wqkv.bias is not None)
+            res = x32
+            if i == L - 1 and last_rows is not None:  # output + MLP on the subset rows (:480-488)
+                ctx = ctx.index_select(0, last_rows)
+                res = x32.index_select(0, last_rows)
+            n = ctx.shape[0]
+            out = att.output
+            h = self._linear(ctx, out.dense.weight)
+            seed, off = rng.take(n * cfg.hidden_size) if p_hidden else (0, 0)
+            y32, yb = DF.FusedLayerNorm.apply(h, out.dense.bias, res, out.LayerNorm.weight,
+                                              out.LayerNorm.bias, eps, 0, p_hidden, seed, off,
+                                              True, bf16)
+            mlp = layer.mlp
+            seed, off = rng.take(n * cfg.intermediate_size) if p_hidden else (0, 0)
+            # the GeGLU forward runs in the gated_layers GEMM's epilogue where the kernel allows
+            g = self._linear(yb if bf16 else y32, mlp.gated_layers.weight,
+                             geglu=(p_hidden, seed, off))
+            wo_lp, wo_lpt = self._lp(mlp.wo.weight), self._lp_t(mlp.wo.weight)
+            if DF.geglu_out_fused_ok(g, wo_lp, wo_lpt):
+                # GeGLU + wo as one node: backward = wo's data gradient with the GeGLU backward
+                # in its epilogue (da never in memory), then wo's weight gradient
+                o = DF.geglu_out(g, p_hidden, seed, off, mlp.wo.weight, wo_lp, wo_lpt)
+            else:
+                a = DF.GeGLU.apply(g, p_hidden, seed, off)
+                o = DF.linear(a, mlp.wo.weight, wo_lp, None, w_lpt=wo_lpt)
+            x32, xb = DF.FusedLayerNorm.apply(o, mlp.wo.bias, y32, mlp.layernorm.weight,
+                                              mlp.layernorm.bias, eps, 0, 0.0, 0, 0, True, bf16)
+            xin = xb if bf16 else x32
+        if L == 0 and last_rows is not None:
+            x32, xin = x32.index_select(0, last_rows), xin.index_select(0, last_rows)
+        if last_rows is None and S != S0:
+            d = x32.shape[1]
+            x32 = x32.view(b, S, d)[:, :S0].reshape(b * S0, d)
+            xin = xin.view(b, S, d)[:, :S0].reshape(b * S0, d)
+        return x32, xin
+
+
+class BertModel(nn.Module, _HipEncoder):
+    """Embeddings + encoder (+ pooler). Inside BertForMaskedLM / BertForSequenceClassification it
+    is the parameter container and the owning model runs `encode`; on its own, `forward` is the
+    embedding-extraction path (reference bert_layers.py:587-644 without masked_tokens_mask)."""
+
+    def __init__(self, config, add_pooling_layer=False, precision: str = "bf16",
+                 init_weights: bool = True):
+        super().__init__()
+        config = BertConfig.from_any(config)
         self.config = config
         self.embeddings = BertEmbeddings(config)
         self.encoder = BertEncoder(config)
+        self.pooler = BertPooler(config) if add_pooling_layer else None
+        self._init_hip_encoder(precision)
+        if init_weights:  # an owning model initialises the whole tree once instead
+            _init_bert_weights(self, config.initializer_range)
+            _tag_projections(self.encoder)
+
+    def _bert_model(self):
+        return self
+
+    def forward(self, input_ids, token_type_ids=None, attention_mask=None, position_ids=None,
+                output_all_encoded_layers=False, masked_tokens_mask=None, **kwargs):
+        """-> (sequence_output [b, S, hidden] fp32 with zero rows at [PAD] positions, like the
+        reference's pad_input, pooled_output [b, hidden] fp32 or None)."""
+        if output_all_encoded_layers or masked_tokens_mask is not None:
+            raise NotImplementedError("BertModel.forward: last layer only, no masked_tokens_mask "
+                                      "(the MLM subset path is BertForMaskedLM.mlm_logits)")
+        self._check_inputs(input_ids, token_type_ids, attention_mask)
+        b, S = input_ids.shape
+        x32, xin = self.encode(input_ids)
+        valid = (input_ids != self.config.pad_token_id_mask).unsqueeze(-1)
+        seq = x32.view(b, S, -1) * valid
+        pooled = None
+        if self.pooler is not None:
+            pooled = DF.pooler(xin.view(b, S, -1)[:, 0], self.pooler.dense.weight,
+                               self.pooler.dense.bias)
+        return seq, pooled
 
 
 class BertPredictionHeadTransform(nn.Module):
@@ -173,7 +382,7 @@ class MLMIndex:
                           (self.subset_idx, self.head_idx, self.target, self.flat_masked)))
 
 
-class BertForMaskedLM(nn.Module):
+class BertForMaskedLM(nn.Module, _HipEncoder):
     """Registry "dnabert2" model (reference bert_layers.py:691-850)."""
 
     def __init__(self, config, precision: str = "bf16", **kwargs):
@@ -182,128 +391,25 @@ class BertForMaskedLM(nn.Module):
         if config.is_decoder:
             raise ValueError("BertForMaskedLM needs config.is_decoder=False")
         self.config = config
-        self.bert = BertModel(config, add_pooling_layer=False)
+        self.bert = BertModel(config, add_pooling_layer=False, init_weights=False)
         self.cls = BertOnlyMLMHead(config, self.bert.embeddings.word_embeddings.weight)
         self.hyena_framework = config.hyena_framework
-        self.precision = precision
-        self.dropout_rng = DF.DropoutRNG()
-        self._lp_provider = None  # set by dna_amd.flat.FlatParams for a persistent bf16 copy
-        self._lpt_provider = None  # ... and for the transposed bf16 projection weights
+        self._init_hip_encoder(precision)
         self._init_weights()
-        # projection weights: keep a W^T copy for the data gradient dx = dy . W^T^T, where the
-        # MFMA kernel wants the reduction (out features) % 64 and the output (in features) % 8,
-        # as dna_transpose_bf16 does; other shapes keep the library dgrad
-        for m in self.modules():
-            if isinstance(m, nn.Linear) and m.out_features % 64 == 0 and m.in_features % 8 == 0:
-                m.weight._dna_transpose = True
+        _tag_projections(self)
 
     # -- reference-compatible utilities ------------------------------------------------------
     def _init_weights(self):
-        """BertPreTrainedModel._init_weights semantics: N(0, initializer_range) for Linear and
-        Embedding weights, zero biases, LayerNorm (1, 0), zero padding_idx row."""
-        std = self.config.initializer_range
-        for m in self.modules():
-            if isinstance(m, nn.Linear):
-                nn.init.normal_(m.weight, mean=0.0, std=std)
-                if m.bias is not None:
-                    nn.init.zeros_(m.bias)
-            elif isinstance(m, nn.Embedding):
-                nn.init.normal_(m.weight, mean=0.0, std=std)
-                if m.padding_idx is not None:
-                    with torch.no_grad():
-                        m.weight[m.padding_idx].zero_()
-            elif isinstance(m, nn.LayerNorm):
-                nn.init.ones_(m.weight)
-                nn.init.zeros_(m.bias)
+        _init_bert_weights(self, self.config.initializer_range)
 
     def get_output_embeddings(self):
         return self.cls.predictions.decoder
 
-    def set_precision(self, precision: str):
-        assert precision in ("bf16", "fp32")
-        self.precision = precision
-        return self
-
-    @property
-    def compute_dtype(self):
-        return torch.bfloat16 if self.precision == "bf16" else torch.float32
-
-    def _lp(self, p: torch.Tensor) -> torch.Tensor:
-        """Compute-dtype view of master weight `p` (persistent shadow if a FlatParams owns it)."""
-        if self.precision == "fp32":
-            return p
-        if self._lp_provider is not None:
-            return self._lp_provider(p)
-        return p.detach().to(torch.bfloat16)
-
-    def _lp_t(self, p: torch.Tensor):
-        """Transposed bf16 copy of projection weight `p` (None: the data gradient falls back)."""
-        if self.precision == "fp32" or self._lpt_provider is None:
-            return None
-        return self._lpt_provider(p)
-
-    def _linear(self, x, w, b=None, geglu=None):
-        return DF.linear(x, w, self._lp(w), b, w_lpt=self._lp_t(w), geglu=geglu)
-
     # -- the hot path ------------------------------------------------------------------------
     def mlm_logits(self, input_ids: torch.Tensor, index: MLMIndex) -> torch.Tensor:
         """Compact logits [M, V] of the masked rows (row-major over (b, s)), compute dtype."""
-        cfg = self.config
-        b, S = input_ids.shape
-        T = b * S
-        H = cfg.num_attention_heads
         bf16 = self.precision == "bf16"
-        train = self.training
-        rng = self.dropout_rng
-        p_hidden = cfg.hidden_dropout_prob if train else 0.0
-        if cfg.attention_probs_dropout_prob and train:
-            raise NotImplementedError("attention-probability dropout (reference default 0.0)")
-        eps = cfg.layer_norm_eps
-        ids = input_ids.reshape(-1)
-        key_valid = (ids != cfg.pad_token_id_mask).to(torch.uint8)
-
-        emb = self.bert.embeddings
-        seed, off = rng.take(T * cfg.hidden_size) if p_hidden else (0, 0)
-        x32, xb = DF.EmbeddingLN.apply(ids, emb.word_embeddings.weight,
-                                       emb.token_type_embeddings.weight, emb.LayerNorm.weight,
-                                       emb.LayerNorm.bias, eps, p_hidden, seed, off, True, bf16)
-        xin = xb if bf16 else x32
-        slopes = self.bert.encoder.alibi_slopes
-        L = len(self.bert.encoder.layer)
-        for i, layer in enumerate(self.bert.encoder.layer):
-            att = layer.attention
-            qkv = self._linear(xin, att.self.Wqkv.weight, att.self.Wqkv.bias)
-            ctx = DF.alibi_attention(qkv, key_valid, slopes, b, S, H,
-                                     bias_grad=att.self.Wqkv.bias is not None)
-            res = x32
-            if i == L - 1:  # last layer: output + MLP only on the subset rows (:480-488)
-                ctx = ctx.index_select(0, index.subset_idx)
-                res = x32.index_select(0, index.subset_idx)
-            n = ctx.shape[0]
-            out = att.output
-            h = self._linear(ctx, out.dense.weight)
-            seed, off = rng.take(n * cfg.hidden_size) if p_hidden else (0, 0)
-            y32, yb = DF.FusedLayerNorm.apply(h, out.dense.bias, res, out.LayerNorm.weight,
-                                              out.LayerNorm.bias, eps, 0, p_hidden, seed, off,
-                                              True, bf16)
-            mlp = layer.mlp
-            seed, off = rng.take(n * cfg.intermediate_size) if p_hidden else (0, 0)
-            # the GeGLU forward runs in the gated_layers GEMM's epilogue where the kernel allows
-            g = self._linear(yb if bf16 else y32, mlp.gated_layers.weight,
-                             geglu=(p_hidden, seed, off))
-            wo_lp, wo_lpt = self._lp(mlp.wo.weight), self._lp_t(mlp.wo.weight)
-            if DF.geglu_out_fused_ok(g, wo_lp, wo_lpt):
-                # GeGLU + wo as one node: backward = wo's data gradient with the GeGLU backward
-                # in its epilogue (da never in memory), then wo's weight gradient
-                o = DF.geglu_out(g, p_hidden, seed, off, mlp.wo.weight, wo_lp, wo_lpt)
-            else:
-                a = DF.GeGLU.apply(g, p_hidden, seed, off)
-                o = DF.linear(a, mlp.wo.weight, wo_lp, None, w_lpt=wo_lpt)
-            x32, xb = DF.FusedLayerNorm.apply(o, mlp.wo.bias, y32, mlp.layernorm.weight,
-                                              mlp.layernorm.bias, eps, 0, 0.0, 0, 0, True, bf16)
-            xin = xb if bf16 else x32
-        if L == 0:
-            xin = xin.index_select(0, index.subset_idx)
+        _, xin = self.encode(input_ids, index.subset_idx)
         seq = xin.index_select(0, index.head_idx)
         tr = self.cls.predictions.transform
         t = self._linear(seq, tr.dense.weight)
@@ -356,3 +462,83 @@ class BertForMaskedLM(nn.Module):
             return MaskedLMOutput(loss=loss, logits=(scores, batch[1]), hidden_states=None,
                                   attentions=None), None
         return MaskedLMOutput(loss=loss, logits=scores, hidden_states=None, attentions=None)
+
+
+class BertForSequenceClassification(nn.Module, _HipEncoder):
+    """DNABERT-2 with the sequence classification / regression head (reference
+    bert_layers.py:881-1009; every DNABERT-2 experiment config maps
+    AutoModelForSequenceClassification to it). Same module tree and state_dict keys: `bert.*`
+    with `bert.pooler.dense.*`, `classifier.*`, no `cls.*`.
+
+    Only the [CLS] row reaches the head, so the last layer's output projection, MLP and
+    LayerNorms run on the b first-column rows alone; pooler, dropout, classifier and loss are
+    the fused head kernels (DF.ClsHead) on the fp32 parameters in both precisions."""
+
+    def __init__(self, config, precision: str = "bf16", **kwargs):
+        super().__init__()
+        config = BertConfig.from_any(config)
+        if config.is_decoder:
+            raise ValueError("BertForSequenceClassification needs config.is_decoder=False")
+        self.config = config
+        self.num_labels = int(config.num_labels)
+        self.bert = BertModel(config, add_pooling_layer=True, init_weights=False)
+        self.classifier_dropout = (config.classifier_dropout if config.classifier_dropout
+                                   is not None else config.hidden_dropout_prob)
+        self.dropout = nn.Dropout(self.classifier_dropout)
+        self.classifier = nn.Linear(config.hidden_size, self.num_labels)
+        self._init_hip_encoder(precision)
+        _init_bert_weights(self, config.initializer_range)
+        _tag_projections(self, skip=(self.classifier, self.bert.pooler.dense))
+        self.last_pred = None  # argmax of the last single-label forward with labels (metrics)
+
+    @classmethod
+    def from_composer(cls, pretrained_checkpoint, state_dict=None, cache_dir=None, from_tf=False,
+                      config=None, *inputs, **kwargs):
+        """Load from a pre-trained checkpoint, non-strictly, with a `model.` prefix stripped
+        (reference :903-933)."""
+        model = cls(config, *inputs, **kwargs)
+        if from_tf:
+            raise ValueError("Mosaic BERT does not support loading TensorFlow weights.")
+        sd = torch.load(pretrained_checkpoint, map_location="cpu", weights_only=True)
+        sd = {(k[len("model."):] if k.startswith("model.") else k): v for k, v in sd.items()}
+        missing, unexpected = model.load_state_dict(sd, strict=False)
+        model.missing_keys, model.unexpected_keys = list(missing), list(unexpected)
+        return model
+
+    def _problem_type(self, labels):
+        cfg = self.config
+        if cfg.problem_type is None:  # reference :977-984
+            if self.num_labels == 1:
+                cfg.problem_type = "regression"
+            elif self.num_labels > 1 and labels.dtype in (torch.long, torch.int):
+                cfg.problem_type = "single_label_classification"
+            else:
+                cfg.problem_type = "multi_label_classification"
+        return cfg.problem_type
+
+    def cls_logits(self, input_ids, labels=None, full_last_layer=False):
+        """(logits [b, num_labels] fp32, loss | None, pred | None). full_last_layer: run the last
+        layer on every row and read the [CLS] rows of its output in place (the reference's
+        computation; the default restricts the last layer to those rows)."""
+        b, S = input_ids.shape
+        rows = torch.arange(b, device=input_ids.device) * S
+        if full_last_layer:
+            _, xin = self.encode(input_ids)
+            x = xin.view(b, S, -1)[:, 0]
+        else:
+            _, x = self.encode(input_ids, rows)
+        p = float(self.classifier_dropout) if self.training else 0.0
+        pool = self.bert.pooler.dense
+        return DF.cls_head(x, pool.weight, pool.bias, self.classifier.weight, self.classifier.bias,
+                           p, self.dropout_rng, labels,
+                           None if labels is None else self._problem_type(labels))
+
+    def forward(self, input_ids=None, attention_mask=None, token_type_ids=None, position_ids=None,
+                head_mask=None, inputs_embeds=None, labels=None, output_attentions=None,
+                output_hidden_states=None, return_dict=None):
+        self._check_inputs(input_ids, token_type_ids, attention_mask)
+        logits, loss, self.last_pred = self.cls_logits(input_ids, labels)
+        if return_dict is not None and not return_dict:
+            return ((loss, logits) if loss is not None else (logits,))
+        return SequenceClassifierOutput(loss=loss, logits=logits, hidden_states=None,
+                                        attentions=None)

@@ -6,6 +6,7 @@ additions (configuration_bert.py:9-25), with the same defaults for the keys the 
 """
 import math
 from dataclasses import dataclass, fields
+from typing import Optional
 
 
 def alibi_slopes(n_heads: int):
@@ -42,6 +43,10 @@ class BertConfig:
     # the attention mask is `input_ids != tokenizer.pad_token_id` (bert_layers.py:786-787);
     # DNABERT-2's tokenizer [PAD] is 3 -- kept separate from the embedding padding_idx above.
     pad_token_id_mask: int = 3
+    # BertForSequenceClassification (bert_layers.py:888-898, :977-984; transformers defaults)
+    num_labels: int = 2
+    classifier_dropout: Optional[float] = None  # None: hidden_dropout_prob
+    problem_type: Optional[str] = None          # None: inferred from num_labels / label dtype
 
     @classmethod
     def from_any(cls, cfg):

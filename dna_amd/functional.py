@@ -7,6 +7,7 @@ No CPU fallback: every op raises if the native library is missing or a tensor is
 """
 import math
 import os
+import warnings
 
 import torch
 import torch.nn as nn
@@ -644,6 +645,169 @@ class MaskedCrossEntropy(torch.autograd.Function):
         return dl, None, None
 
 
+# ----------------------------------------------------------------------------------- cls head
+CLS_PROBLEMS = {"regression": N.CLS_REGRESSION, "single_label_classification": N.CLS_SINGLE_LABEL,
+                "multi_label_classification": N.CLS_MULTI_LABEL}
+
+
+def _cls_rows(x):
+    """x as B rows of H with unit column stride (a strided row view is read in place)."""
+    if x.dim() != 2:
+        raise ValueError(f"dna_amd: cls head input must be [B, H], got {tuple(x.shape)}")
+    if x.stride(1) != 1 or (x.shape[0] > 1 and x.stride(0) < x.shape[1]):
+        x = x.contiguous()
+    return x, (x.stride(0) if x.shape[0] > 1 else x.shape[1])
+
+
+def _cls_labels(labels, problem, B, C):
+    if problem == N.CLS_SINGLE_LABEL:
+        labels = labels.reshape(-1).to(torch.int64).contiguous()
+        if labels.numel() != B:
+            raise ValueError(f"dna_amd: {labels.numel()} labels for a batch of {B}")
+        return labels
+    labels = labels.to(torch.float32).reshape(-1).contiguous()
+    if labels.numel() != B * C:
+        raise ValueError(f"dna_amd: {labels.numel()} label values for logits [{B}, {C}]")
+    return labels
+
+
+def _f32_param(name, t, shape):
+    if t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != tuple(shape):
+        raise TypeError(f"dna_amd: cls head {name} must be contiguous fp32 {tuple(shape)}, got "
+                        f"{t.dtype} {tuple(t.shape)}")
+
+
+class ClsHead(torch.autograd.Function):
+    """BertPooler + dropout + classifier (+ loss) of BertForSequenceClassification (reference
+    bert_layers.py:495-510, :969-998) on csrc/cls_head.hip:
+
+        t = tanh(x Wp^T + bp);  a = dropout(t; p, seed, off);  logits = a Wc^T + bc
+        -> (logits [B, C] fp32, loss scalar | None, pred [B] int64 | None)
+
+    x [B, H] fp32 or bf16, rows may be strided (the [CLS] rows of a [b*S, H] activation read in
+    place); the weights are the fp32 master parameters in both precisions. labels None: logits
+    only. Forward 2 launches (the loss rides in the second), backward 2; with FlatParams direct
+    gradients the four parameter gradients are added straight into the flat buffer."""
+
+    @staticmethod
+    def forward(ctx, x, wp, bp, wc, bc, p, seed, off, labels, problem):
+        _gpu(x, wp, bp, wc, bc, labels)
+        ctx.set_materialize_grads(False)
+        x, stride = _cls_rows(x)
+        B, H = x.shape
+        C = wc.shape[0]
+        _f32_param("pooler weight", wp, (H, H))
+        _f32_param("pooler bias", bp, (H,))
+        _f32_param("classifier weight", wc, (C, H))
+        _f32_param("classifier bias", bc, (C,))
+        dev = x.device
+        t = torch.empty(B, H, device=dev, dtype=torch.float32)
+        a = torch.empty_like(t)
+        logits = torch.empty(B, C, device=dev, dtype=torch.float32)
+        loss = dl = pred = None
+        if labels is not None:
+            labels = _cls_labels(labels, problem, B, C)
+            loss = torch.empty(1, device=dev, dtype=torch.float32)
+            dl = torch.empty_like(logits)
+            if problem == N.CLS_SINGLE_LABEL:
+                pred = torch.empty(B, device=dev, dtype=torch.int64)
+        nws = N.lib().dna_cls_head_fwd_workspace(B, H, C)
+        ws = torch.empty(max(nws // 4, 4), device=dev, dtype=torch.float32)
+        with _timed("cls_head_fwd", 2.0 * B * H * (H + C)):
+            N.call("dna_cls_head_fwd", x.data_ptr(), _dt(x), stride, wp.data_ptr(), bp.data_ptr(),
+                   wc.data_ptr(), bc.data_ptr(), B, H, C, float(p), seed, off, t.data_ptr(),
+                   a.data_ptr(), logits.data_ptr(), _p(labels), problem, _p(loss), _p(dl), _p(pred),
+                   ws.data_ptr(), ws.numel() * 4, N.stream_ptr())
+        ctx.save_for_backward(x, wp, wc, t, a, dl)
+        ctx.params = (wp, bp, wc, bc)
+        ctx.cfg = (stride, float(p), seed, off)
+        if pred is not None:
+            ctx.mark_non_differentiable(pred)
+        return logits, (None if loss is None else loss.reshape(())), pred
+
+    @staticmethod
+    def backward(ctx, dlogits, dloss, dpred):
+        x, wp, wc, t, a, dl = ctx.saved_tensors
+        stride, p, seed, off = ctx.cfg
+        up = None
+        if dl is not None and dloss is not None:
+            if dlogits is None:  # the usual case: only the loss was used
+                g, up = dl, dloss.detach().to(torch.float32).reshape(1).contiguous()
+            else:
+                g = (dl * dloss + dlogits).contiguous()
+        elif dlogits is not None:
+            g = dlogits.to(torch.float32).contiguous()
+        else:
+            return (None,) * 10
+        B, H = x.shape
+        C = wc.shape[0]
+        dev = x.device
+        pwp, pbp, pwc, pbc = ctx.params
+        direct = _param_grads_direct(ctx.params)
+        if direct:
+            dwp, dbp, dwc, dbc = pwp.grad, pbp.grad, pwc.grad, pbc.grad
+        else:
+            dwp, dbp = torch.empty_like(wp), torch.empty(H, device=dev, dtype=torch.float32)
+            dwc, dbc = torch.empty_like(wc), torch.empty(C, device=dev, dtype=torch.float32)
+        dx = torch.empty(B, H, device=dev, dtype=torch.float32)
+        nws = N.lib().dna_cls_head_bwd_workspace(B, H, C)
+        ws = torch.empty(max(nws // 4, 4), device=dev, dtype=torch.float32)
+        with _timed("cls_head_bwd", 4.0 * B * H * (H + C)):
+            N.call("dna_cls_head_bwd", g.data_ptr(), _p(up), x.data_ptr(), _dt(x), stride,
+                   t.data_ptr(), a.data_ptr(), wp.data_ptr(), wc.data_ptr(), B, H, C, p, seed, off,
+                   dwc.data_ptr(), dbc.data_ptr(), dwp.data_ptr(), dbp.data_ptr(), dx.data_ptr(),
+                   int(direct), ws.data_ptr(), ws.numel() * 4, N.stream_ptr())
+        dx = dx if x.dtype == torch.float32 else dx.to(x.dtype)
+        if direct:
+            for q in ctx.params:
+                notify = getattr(q, "_dna_notify", None)
+                if notify is not None:
+                    notify(q)
+            return (dx,) + (None,) * 9
+        return dx, dwp, dbp, dwc, dbc, None, None, None, None, None
+
+
+_POOLER_WARNED = False
+
+
+def pooler(x, wp, bp):
+    """tanh(x wp^T + bp) [B, H] fp32 (BertPooler, reference bert_layers.py:495-510) from the head
+    kernel's first stage, for embedding extraction. The result carries no autograd graph
+    (training goes through ClsHead, which has the backward); where one would have been recorded
+    -- grad mode on and an input that requires grad -- a warning says so, once."""
+    if torch.is_grad_enabled() and (x.requires_grad or wp.requires_grad or bp.requires_grad):
+        global _POOLER_WARNED
+        if not _POOLER_WARNED:
+            _POOLER_WARNED = True
+            warnings.warn("dna_amd: BertModel's pooled_output is computed without an autograd "
+                          "graph (embedding extraction); train the pooler through "
+                          "BertForSequenceClassification", stacklevel=2)
+    _gpu(x, wp, bp)
+    x, stride = _cls_rows(x)
+    B, H = x.shape
+    _f32_param("pooler weight", wp, (H, H))
+    _f32_param("pooler bias", bp, (H,))
+    t = torch.empty(B, H, device=x.device, dtype=torch.float32)
+    a = torch.empty_like(t)
+    wc = torch.zeros(1, H, device=x.device, dtype=torch.float32)  # a one-label classifier of zeros
+    logits = torch.empty(B, 1, device=x.device, dtype=torch.float32)
+    nws = N.lib().dna_cls_head_fwd_workspace(B, H, 1)
+    ws = torch.empty(max(nws // 4, 4), device=x.device, dtype=torch.float32)
+    N.call("dna_cls_head_fwd", x.data_ptr(), _dt(x), stride, wp.data_ptr(), bp.data_ptr(),
+           wc.data_ptr(), wc.data_ptr(), B, H, 1, 0.0, 0, 0, t.data_ptr(), a.data_ptr(),
+           logits.data_ptr(), None, 0, None, None, None, ws.data_ptr(), ws.numel() * 4,
+           N.stream_ptr())
+    return t
+
+
+def cls_head(x, wp, bp, wc, bc, p=0.0, rng=None, labels=None, problem_type=None):
+    """ClsHead with the dropout draw: rng.take(B * H) only when p > 0. problem_type: a
+    CLS_PROBLEMS name (needed with labels). -> (logits, loss | None, pred | None)."""
+    seed, off = rng.take(x.shape[0] * x.shape[1]) if p > 0 else (0, 0)
+    problem = CLS_PROBLEMS[problem_type] if labels is not None else N.CLS_SINGLE_LABEL
+    return ClsHead.apply(x, wp, bp, wc, bc, float(p), seed, off, labels, problem)
+
+
 # ----------------------------------------------------------------------------------- GEMM
 def _gemm_impl():
     """"hip" (default): forward and data-gradient GEMMs on csrc/gemm.hip; "torch": hipBLASLt
@@ -977,6 +1141,25 @@ def _hip_wgrad_ok(dy, x):
             and os.environ.get("DNA_WGRAD_IMPL", "hip") == "hip")
 
 
+def _small_wgrad_ok(dy, x):
+    """A handful of rows (the [CLS] rows of a fine-tuning batch in the last layer, the masked rows
+    of a tiny micro-batch): below dna_linear_wgrad_p's two 64-row K-steps per split, so dW runs
+    on the strided MFMA GEMM (dna_gemm_bf16_strided, fp32 out, any shape) instead of a library
+    GEMM."""
+    return (dy.dtype == torch.bfloat16 and x.dtype == torch.bfloat16 and dy.is_cuda
+            and 1 <= dy.shape[0] < 128 and _gemm_impl() == "hip"
+            and os.environ.get("DNA_WGRAD_IMPL", "hip") == "hip")
+
+
+def _small_wgrad(dy, x, out, accumulate):
+    """out[m, n] (+)= dy[rows, m]^T x[rows, n], fp32 out, one launch."""
+    dy, x = dy.contiguous(), x.contiguous()
+    rows, m = dy.shape
+    n = x.shape[1]
+    strided_gemm(dy, (1, m, 0), x, (n, 1, 0), out, (n, 0), m, n, rows, 1, out_f32=True,
+                 accumulate=accumulate)
+
+
 def _hip_wgrad_parts(dy, x):
     """fp32 split-K partials [s, m, n] of dy^T x from the persistent MFMA kernel (token-major
     operands read in place; s chosen by the library to fill the grid)."""
@@ -1006,6 +1189,10 @@ def wgrad(dy, x):
         out = torch.empty(parts.shape[1:], device=dy.device, dtype=torch.float32)
         N.call("dna_sum_slices", parts.data_ptr(), s, out.numel(), out.data_ptr(), N.stream_ptr())
         return out
+    if _small_wgrad_ok(dy, x):
+        out = torch.empty(dy.shape[1], x.shape[1], device=dy.device, dtype=torch.float32)
+        _small_wgrad(dy, x, out, False)
+        return out
     library_fallback("weight gradient", dy.shape, x.shape)
     rows, m = dy.shape
     n = x.shape[1]
@@ -1027,6 +1214,9 @@ def wgrad_accumulate(dy, x, grad):
         parts, s = _hip_wgrad_parts(dy, x)
         N.call("dna_sum_slices_accum", parts.data_ptr(), s, m * n, grad.data_ptr(), N.stream_ptr())
         return
+    if _small_wgrad_ok(dy, x):
+        _small_wgrad(dy, x, grad, True)
+        return
     library_fallback("weight gradient", dy.shape, x.shape)
     s = wgrad_splits(rows, m, n)
     if s == 1:
@@ -1041,7 +1231,7 @@ def _weight_grad(w, dy, x, flops):
     """dW = dy^T x of the projection with fp32 master weight w: straight into the flat gradient
     buffer when a FlatParams owns w (None returned, bucket reducer notified), else returned."""
     direct = (getattr(w, "_dna_direct", False) and w.grad is not None and x.dtype != torch.float32
-              and _hip_wgrad_ok(dy, x))
+              and (_hip_wgrad_ok(dy, x) or _small_wgrad_ok(dy, x)))
     side = _side_stream() if direct else None
     if side is not None:
         # wgrad beside the rest of the backward; dy / x must outlive it on the side stream

@@ -14,6 +14,10 @@ asserts (flash_attn_triton.py:849-855) -- instead of letting a kernel read out o
     torch.ops.dna_amd.geglu_bwd(da, fac, dg)                      dg = da * fac
     torch.ops.dna_amd.xent_fwd(logits, target, loss, lse)         per-row CE
     torch.ops.dna_amd.transpose_bf16(src, dst)
+    torch.ops.dna_amd.cls_head_fwd(x, wp, bp, wc, bc, p, seed, offset, t, a, logits)
+    torch.ops.dna_amd.cls_loss(logits, labels, problem_type, loss, dlogits, pred)
+    torch.ops.dna_amd.cls_head_bwd(dlogits, x, t, a, wp, wc, p, seed, offset, dwc, dbc, dwp, dbp,
+                                   dx, accumulate)
 and the reference's FlashAttention kernel slot with its own signature (flash_attn_triton.py:
 1077-1130, called at bert_layers.py:188/192 as flash_attn_qkvpacked_func(qkv, bias)), autograd
 included:
@@ -355,6 +359,81 @@ def xent_fwd(logits: torch.Tensor, target: torch.Tensor, loss: torch.Tensor,
            loss.data_ptr(), lse.data_ptr(), N.stream_ptr())
 
 
+# ------------------------------------------------------------------------------- cls head
+def _cls_x(x):
+    _check(x.is_cuda, f"x must be on the GPU (no CPU fallback), got {x.device}")
+    _check(x.dtype in _DT, f"x dtype {x.dtype} not in {tuple(_DT)}")
+    _check(x.dim() == 2 and x.stride(1) == 1 and (x.shape[0] == 1 or x.stride(0) >= x.shape[1]),
+           "x must be [B, H] rows with unit column stride")
+    return x.stride(0) if x.shape[0] > 1 else x.shape[1]
+
+
+@torch.library.custom_op("dna_amd::cls_head_fwd", mutates_args=("t", "a", "logits"))
+def cls_head_fwd(x: torch.Tensor, wp: torch.Tensor, bp: torch.Tensor, wc: torch.Tensor,
+                 bc: torch.Tensor, p: float, seed: int, offset: int, t: torch.Tensor,
+                 a: torch.Tensor, logits: torch.Tensor) -> None:
+    """t = tanh(x wp^T + bp), a = dropout(t; p, seed, offset), logits = a wc^T + bc (fp32
+    parameters; x fp32 or bf16 rows, a strided row view is read in place)."""
+    stride = _cls_x(x)
+    B, H = x.shape
+    C = wc.shape[0]
+    for n, w, shape in (("wp", wp, (H, H)), ("bp", bp, (H,)), ("wc", wc, (C, H)), ("bc", bc, (C,)),
+                        ("t", t, (B, H)), ("a", a, (B, H)), ("logits", logits, (B, C))):
+        _cuda_contig(n, w, (torch.float32,))
+        _check(tuple(w.shape) == shape, f"{n} must be {shape}, got {tuple(w.shape)}")
+    nws = N.lib().dna_cls_head_fwd_workspace(B, H, C)
+    ws = torch.empty(max(nws // 4, 4), device=x.device, dtype=torch.float32)
+    N.call("dna_cls_head_fwd", x.data_ptr(), _DT[x.dtype], stride, wp.data_ptr(), bp.data_ptr(),
+           wc.data_ptr(), bc.data_ptr(), B, H, C, float(p), seed, offset, t.data_ptr(),
+           a.data_ptr(), logits.data_ptr(), None, 0, None, None, None, ws.data_ptr(),
+           ws.numel() * 4, N.stream_ptr())
+
+
+@torch.library.custom_op("dna_amd::cls_loss", mutates_args=("loss", "dlogits", "pred"))
+def cls_loss(logits: torch.Tensor, labels: torch.Tensor, problem_type: int, loss: torch.Tensor,
+             dlogits: torch.Tensor, pred: torch.Tensor | None) -> None:
+    """problem_type 0 regression (MSE), 1 single-label (mean CE, int64 labels [B]; pred = argmax),
+    2 multi-label (BCE with logits); fp32 labels [B, C] for 0 and 2. loss: one float, dlogits:
+    d loss / d logits."""
+    _cuda_contig("logits", logits, (torch.float32,))
+    B, C = logits.shape
+    _cuda_contig("labels", labels, (torch.int64,) if problem_type == 1 else (torch.float32,))
+    _check(labels.numel() == (B if problem_type == 1 else B * C), "label count")
+    _cuda_contig("loss", loss, (torch.float32,))
+    _cuda_contig("dlogits", dlogits, (torch.float32,))
+    _check(loss.numel() == 1 and dlogits.shape == logits.shape, "loss [1], dlogits like logits")
+    if pred is not None:
+        _cuda_contig("pred", pred, (torch.int64,))
+        _check(pred.numel() == B, "pred must hold B entries")
+    N.call("dna_cls_loss", logits.data_ptr(), labels.data_ptr(), problem_type, B, C,
+           loss.data_ptr(), dlogits.data_ptr(), _p(pred), N.stream_ptr())
+
+
+@torch.library.custom_op("dna_amd::cls_head_bwd",
+                         mutates_args=("dwc", "dbc", "dwp", "dbp", "dx"))
+def cls_head_bwd(dlogits: torch.Tensor, x: torch.Tensor, t: torch.Tensor, a: torch.Tensor,
+                 wp: torch.Tensor, wc: torch.Tensor, p: float, seed: int, offset: int,
+                 dwc: torch.Tensor, dbc: torch.Tensor, dwp: torch.Tensor, dbp: torch.Tensor,
+                 dx: torch.Tensor, accumulate: bool) -> None:
+    """Backward of cls_head_fwd from dlogits: dwc, dbc, dwp, dbp (accumulate: added into the
+    buffers) and dx [B, H] fp32."""
+    stride = _cls_x(x)
+    B, H = x.shape
+    C = wc.shape[0]
+    for n, w, shape in (("dlogits", dlogits, (B, C)), ("t", t, (B, H)), ("a", a, (B, H)),
+                        ("wp", wp, (H, H)), ("wc", wc, (C, H)), ("dwc", dwc, (C, H)),
+                        ("dbc", dbc, (C,)), ("dwp", dwp, (H, H)), ("dbp", dbp, (H,)),
+                        ("dx", dx, (B, H))):
+        _cuda_contig(n, w, (torch.float32,))
+        _check(tuple(w.shape) == shape, f"{n} must be {shape}, got {tuple(w.shape)}")
+    nws = N.lib().dna_cls_head_bwd_workspace(B, H, C)
+    ws = torch.empty(max(nws // 4, 4), device=x.device, dtype=torch.float32)
+    N.call("dna_cls_head_bwd", dlogits.data_ptr(), None, x.data_ptr(), _DT[x.dtype], stride,
+           t.data_ptr(), a.data_ptr(), wp.data_ptr(), wc.data_ptr(), B, H, C, float(p), seed,
+           offset, dwc.data_ptr(), dbc.data_ptr(), dwp.data_ptr(), dbp.data_ptr(), dx.data_ptr(),
+           int(accumulate), ws.data_ptr(), ws.numel() * 4, N.stream_ptr())
+
+
 OPS = ("attn_fwd", "attn_bwd", "alibi_attn_qkvpacked", "flash_attn_qkvpacked", "linear_fwd",
        "transpose_bf16", "geglu_linear_fwd", "geglu_linear_dgrad",
-       "geglu_fwd", "geglu_bwd", "xent_fwd")
+       "geglu_fwd", "geglu_bwd", "xent_fwd", "cls_head_fwd", "cls_loss", "cls_head_bwd")

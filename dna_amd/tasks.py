@@ -65,6 +65,53 @@ class NumTokens:
         return self.count
 
 
+class ConfusionMatrix:
+    """[C, C] int64 counts (rows: label, columns: prediction) accumulated on the device of the
+    inputs -- no host sync per batch -- from the head's `pred` and the labels. compute() at epoch
+    end gives accuracy, the multi-class Matthews correlation coefficient and macro F1 over the
+    pooled predictions of the epoch (what the GUE tables report; equal to
+    sklearn.metrics.matthews_corrcoef / f1_score(average="macro") on them). The reference calls
+    sklearn per batch instead and averages the per-batch values (src/tasks/metrics.py:83-87,
+    :229-233)."""
+
+    def __init__(self, num_classes):
+        self.num_classes = int(num_classes)
+        self.reset()
+
+    def reset(self):
+        self.counts = torch.zeros(self.num_classes, self.num_classes, dtype=torch.int64)
+
+    def update(self, pred, target):
+        """counts[target, pred] += 1 for every pair: an index_add_ into the preallocated matrix,
+        which reads nothing back to the host (torch.bincount would, to size its output). Labels
+        and predictions must lie in [0, num_classes); that is not checked here, for the same
+        reason."""
+        C = self.num_classes
+        idx = target.reshape(-1).to(torch.int64) * C + pred.reshape(-1).to(torch.int64)
+        if self.counts.device != idx.device:  # once: the matrix moves to where the batches are
+            self.counts = self.counts.to(idx.device)
+        self.counts.view(-1).index_add_(0, idx, torch.ones_like(idx))
+
+    def compute(self):
+        m = self.counts.to(torch.float64).cpu()
+        n = m.sum()
+        tp = m.diag()
+        t, p = m.sum(1), m.sum(0)  # per class: how often it is the label / the prediction
+        acc = (tp.sum() / n).item() if n > 0 else 0.0
+        # Gorodkin's R_K, as sklearn.metrics.matthews_corrcoef
+        cov_tp = tp.sum() * n - (t * p).sum()
+        cov_pp = n * n - (p * p).sum()
+        cov_tt = n * n - (t * t).sum()
+        den = cov_pp * cov_tt
+        mcc = (cov_tp / den.sqrt()).item() if den > 0 else 0.0
+        # macro F1 over the classes that occur as a label or a prediction (sklearn's label set);
+        # a class with no true positive scores 0
+        present = (t + p) > 0
+        f1 = torch.where(tp > 0, 2 * tp / (t + p).clamp(min=1), torch.zeros_like(tp))
+        f1_macro = f1[present].mean().item() if present.any() else 0.0
+        return {"accuracy": acc, "mcc": mcc, "f1_macro": f1_macro}
+
+
 torchmetric_fns = {"perplexity": Perplexity, "num_tokens": NumTokens}
 
 

@@ -13,7 +13,7 @@ from dataclasses import dataclass
 import torch
 import torch.distributed as dist
 
-from .bert_layers import BertForMaskedLM, MLMIndex
+from .bert_layers import BertForMaskedLM, BertForSequenceClassification, MLMIndex
 from .ddp import GradBucketReducer, broadcast_
 from .flat import FlatParams
 from .optim import FusedAdamW, LinearLRSchedulerWarmup
@@ -167,3 +167,73 @@ class MLMTrainer:
             self.sched.step()
         self.global_step += 1
         return total
+
+
+def load_backbone(model, path):
+    """Load a Lightning-layout MLM checkpoint (train.py save_checkpoint: {"state_dict":
+    {"model.<key>": ...}}; a bare state dict works too) into a BertForSequenceClassification,
+    non-strictly. -> (missing keys, unexpected keys): for an MLM checkpoint the pooler and
+    classifier keys (they keep their initialisation) and the `cls.*` MLM-head keys."""
+    ck = torch.load(path, map_location="cpu", weights_only=True)
+    sd = ck.get("state_dict", ck)
+    sd = {(k[len("model."):] if k.startswith("model.") else k): v for k, v in sd.items()}
+    missing, unexpected = model.load_state_dict(sd, strict=False)
+    return list(missing), list(unexpected)
+
+
+class ClsTrainer:
+    """Fine-tuning step engine for BertForSequenceClassification, next to MLMTrainer: flat fp32
+    parameters / gradients with the bf16 shadow, the fused head kernels writing their parameter
+    gradients straight into the flat buffer, global-norm clip + AdamW in one launch, LR schedule,
+    dropout-stream state for checkpoints. Single GPU (multi-rank fine-tuning is not built)."""
+
+    def __init__(self, model: BertForSequenceClassification, device, lr=3e-5, weight_decay=0.01,
+                 betas=(0.9, 0.999), eps=1e-8, max_grad_norm=1.0, scheduler=None, seed=None):
+        if dist.is_initialized() and dist.get_world_size() > 1:
+            raise NotImplementedError("ClsTrainer: single-GPU fine-tuning only")
+        self.model = model.to(device).train()
+        self.device = device
+        self.flat = FlatParams(self.model, device)
+        self.flat.enable_direct_grad(True)
+        self.opt = FusedAdamW(self.flat, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay,
+                              max_grad_norm=max_grad_norm)
+        self.sched = LinearLRSchedulerWarmup(self.opt, **scheduler) if scheduler else None
+        base = self.model.dropout_rng.seed if seed is None else int(seed) + 0x5EED
+        self.model.dropout_rng.seed = (base * 1000003) & (2 ** 63 - 1)
+        self.global_step = 0
+        self._versions = _sync_shadow(self.flat, None)
+        self.last_logits = None
+        self.last_pred = None
+
+    def rng_state(self):
+        r = self.model.dropout_rng
+        return {"seed": int(r.seed), "offset": int(r.offset)}
+
+    def load_rng_state(self, st):
+        self.model.dropout_rng.seed = int(st["seed"])
+        self.model.dropout_rng.offset = int(st["offset"])
+
+    def step(self, input_ids, labels) -> torch.Tensor:
+        """One optimizer step on one batch (ids [b, S] and labels on the device). The logits and
+        (single-label) predictions of the step stay in last_logits / last_pred; no host sync."""
+        self._versions = _sync_shadow(self.flat, self._versions)
+        self.opt.zero_grad()
+        logits, loss, pred = self.model.cls_logits(input_ids, labels)
+        loss.backward()
+        self.opt.step()
+        if self.sched is not None:
+            self.sched.step()
+        self.global_step += 1
+        self.last_logits, self.last_pred = logits.detach(), pred
+        return loss.detach()
+
+    @torch.no_grad()
+    def evaluate(self, input_ids, labels=None):
+        """Eval-mode forward -> (logits, loss | None, pred | None); restores the training mode."""
+        was = self.model.training
+        self.model.eval()
+        try:
+            self._versions = _sync_shadow(self.flat, self._versions)
+            return self.model.cls_logits(input_ids, labels)
+        finally:
+            self.model.train(was)

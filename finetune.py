@@ -1,0 +1,182 @@
+#!/usr/bin/env python
+"""Fine-tune DNABERT-2 for sequence classification on a GUE-layout folder (single GPU).
+
+    python finetune.py dataset.data_dir=/data/GUE/prom/prom_300_all \\
+        train.pretrained_model_path=checkpoints/last.ckpt trainer.max_epochs=3
+    python finetune.py --dry-run                       # compose + build, no GPU
+
+`key=value` overrides are composed by dna_amd.compose over configs/ with the experiment
+dnabert2/dnabert2_gue_finetune (another one: experiment=...). The run trains with ClsTrainer
+(HIP encoder + fused classification head, AdamW, linear warmup), evaluates dev and test after every
+epoch (loss, accuracy, MCC, macro F1 over the pooled predictions of the split), prints one JSON
+line per event, and writes the best (train.monitor / train.mode, default val/mcc max) and last
+checkpoints in train.py's Lightning layout. train.pretrained_model_path takes an MLM checkpoint
+written by train.py (the MLM head is dropped, pooler and classifier start from their
+initialisation) or a fine-tuning checkpoint.
+"""
+import argparse
+import json
+import os
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, ROOT)
+
+from dna_amd.compose import compose  # noqa: E402
+
+EXPERIMENT = "dnabert2/dnabert2_gue_finetune"
+
+
+def _model_config(cfg, num_labels=None):
+    mc = cfg.model.config.to_container()
+    if mc.get("num_labels") is None:
+        mc["num_labels"] = int(num_labels) if num_labels else 2
+    return mc
+
+
+def _scheduler(cfg):
+    if "scheduler" not in cfg or cfg.scheduler is None:
+        return None
+    if cfg.scheduler._name_ != "linear_warmup":
+        raise NotImplementedError(f"scheduler {cfg.scheduler._name_!r} (linear_warmup only)")
+    return {k: v for k, v in cfg.scheduler.to_container().items() if k != "_name_"}
+
+
+@torch.no_grad()
+def evaluate(trainer, ds, batch_size, device, num_labels):
+    """-> {"loss", "accuracy", "mcc", "f1_macro"} of one split; counts stay on the device until
+    the split is done."""
+    from dna_amd.tasks import ConfusionMatrix
+    cm = ConfusionMatrix(num_labels)
+    total = torch.zeros((), device=device, dtype=torch.float64)
+    for i in range(0, len(ds), batch_size):
+        items = [ds[j] for j in range(i, min(i + batch_size, len(ds)))]
+        ids, labels = ds.collate(items)
+        ids, labels = ids.to(device), labels.to(device)
+        _, loss, pred = trainer.evaluate(ids, labels)
+        total += loss.double() * len(items)
+        cm.update(pred, labels)
+    out = cm.compute()
+    out["loss"] = (total / max(len(ds), 1)).item()
+    return out
+
+
+def finetune(cfg, dry_run=False, out=sys.stdout):
+    import train as T
+    from dna_amd.bert_layers import BertForSequenceClassification
+    from dna_amd.finetune_data import SequenceClassificationCSV
+    from dna_amd.trainer import ClsTrainer, load_backbone
+
+    if cfg.model._name_ != "dnabert2_cls":
+        raise ValueError(f"model._name_={cfg.model._name_!r}: finetune.py runs dnabert2_cls")
+    if T.n_devices(cfg.trainer) != 1:
+        raise NotImplementedError("finetune.py: single-GPU fine-tuning only (trainer.devices=1)")
+    seed = cfg.train.get("seed")
+    if seed is not None:
+        torch.manual_seed(int(seed))
+    problem = cfg.model.config.get("problem_type") or "single_label_classification"
+    if problem != "single_label_classification":
+        raise NotImplementedError(
+            f"model.config.problem_type={problem!r}: finetune.py reads integer labels and reports "
+            "accuracy / MCC / F1 from the argmax, i.e. single_label_classification; regression "
+            "and multi-label heads train through ClsTrainer directly")
+    precision = T._precision(cfg.trainer.get("precision", "bf16"))
+    sched = _scheduler(cfg)
+    opt = cfg.optimizer.to_container()
+    data_dir = cfg.dataset.get("data_dir")
+    if dry_run:
+        model = BertForSequenceClassification(_model_config(cfg), precision=precision)
+        print(json.dumps({"dry_run": True, "model": cfg.model._name_,
+                          "model_params": sum(p.numel() for p in model.parameters()),
+                          "num_labels": model.num_labels, "data_dir": data_dir,
+                          "monitor": cfg.train.monitor, "mode": cfg.train.mode,
+                          "scheduler": sched, "optimizer": opt}), file=out)
+        return None
+    if not data_dir:
+        raise ValueError("dataset.data_dir=<folder with train.csv, dev.csv, test.csv> is required")
+
+    max_length = int(cfg.dataset.get("max_length", 128))
+    splits = {s: SequenceClassificationCSV(data_dir, s, max_length) for s in ("train", "dev", "test")}
+    train_ds = splits["train"]
+    model = BertForSequenceClassification(_model_config(cfg, train_ds.num_labels),
+                                          precision=precision)
+    pre = cfg.train.get("pretrained_model_path")
+    if pre:
+        missing, unexpected = load_backbone(model, pre)
+        print(json.dumps({"event": "load_backbone", "path": pre, "missing": missing,
+                          "unexpected": len(unexpected)}), file=out, flush=True)
+    device = torch.device("cuda", 0)
+    torch.cuda.set_device(device)
+    trainer = ClsTrainer(model, device, lr=float(opt.get("lr", 3e-5)),
+                         weight_decay=float(opt.get("weight_decay", 0.01)),
+                         betas=tuple(opt.get("betas", (0.9, 0.999))), eps=float(opt.get("eps", 1e-8)),
+                         max_grad_norm=cfg.trainer.get("gradient_clip_val", 1.0), scheduler=sched,
+                         seed=seed)
+    ck = (cfg.get("callbacks", {}) or {}).get("model_checkpoint")
+    ck = ck.to_container() if ck is not None else {}
+    dirpath = ck.get("dirpath", "checkpoints/")
+    best = T.BestCheckpoint(dirpath, ck.get("monitor", cfg.train.monitor),
+                            ck.get("mode", cfg.train.mode), ck.get("filename"),
+                            ck.get("save_top_k", 1))
+    bs = int(cfg.dataset.get("batch_size", 32))
+    ebs = int(cfg.dataset.get("eval_batch_size", bs))
+    log_every = int(cfg.trainer.get("log_every_n_steps", 10))
+    max_steps = cfg.train.get("max_steps")
+    gen = torch.Generator().manual_seed(int(seed or 0))
+    print(json.dumps({"event": "start", "train": len(train_ds), "dev": len(splits["dev"]),
+                      "test": len(splits["test"]), "num_labels": model.num_labels,
+                      "batch_size": bs}), file=out, flush=True)
+    metrics = {}
+    for epoch in range(int(cfg.trainer.get("max_epochs", 1))):
+        order = (torch.randperm(len(train_ds), generator=gen) if cfg.dataset.get("shuffle", True)
+                 else torch.arange(len(train_ds))).tolist()
+        for i in range(0, len(order), bs):
+            ids, labels = train_ds.collate([train_ds[j] for j in order[i:i + bs]])
+            loss = trainer.step(ids.to(device, non_blocking=True),
+                                labels.to(device, non_blocking=True))
+            if trainer.global_step % log_every == 0:
+                print(json.dumps({"event": "train", "epoch": epoch, "step": trainer.global_step,
+                                  "trainer/loss": loss.item(), "lr": trainer.opt.param_groups[0]["lr"]}),
+                      file=out, flush=True)
+            if max_steps and trainer.global_step >= int(max_steps):
+                break
+        metrics = {}
+        for name, split in (("val", "dev"), ("test", "test")):
+            for k, v in evaluate(trainer, splits[split], ebs, device, model.num_labels).items():
+                metrics[f"{name}/{k}"] = v
+        print(json.dumps(dict({"event": "eval", "epoch": epoch, "step": trainer.global_step},
+                              **metrics)), file=out, flush=True)
+        value = metrics.get(best.monitor)
+        if best.enabled and value is not None and best.improves(value):
+            best.score = value
+            T.save_checkpoint(best.path, trainer, epoch + 1, metrics=metrics, best=best)
+        if ck.get("save_last", True):
+            T.save_checkpoint(os.path.join(dirpath, "last.ckpt"), trainer, epoch + 1,
+                              metrics=metrics, best=best if best.enabled else None)
+        if max_steps and trainer.global_step >= int(max_steps):
+            break
+    return metrics
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--config-dir", default=os.environ.get("DNA_CONFIG_DIR",
+                                                           os.path.join(ROOT, "configs")))
+    ap.add_argument("--config-name", default="config")
+    ap.add_argument("--dry-run", action="store_true", help="compose + build, no training")
+    ap.add_argument("--print-config", action="store_true")
+    ap.add_argument("overrides", nargs="*")
+    a = ap.parse_args(argv)
+    overrides = list(a.overrides)
+    if not any(o.startswith("experiment=") for o in overrides):
+        overrides.insert(0, "experiment=" + EXPERIMENT)
+    cfg = compose(a.config_dir, a.config_name, overrides)
+    if a.print_config or a.dry_run:
+        print(json.dumps(cfg.to_container(skip_errors=True), indent=1, default=str))
+    return finetune(cfg, dry_run=a.dry_run)
+
+
+if __name__ == "__main__":
+    main()

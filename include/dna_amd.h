@@ -499,6 +499,46 @@ int dna_xent_bwd(const void* logits, int dtype, const int64_t* target, const flo
                  const float* dloss, float scale, int rows, int vocab, void* dlogits,
                  void* stream);
 
+/* ------------------------------------------------------------------ sequence-classification head
+ * BertPooler + dropout + classifier + loss of BertForSequenceClassification (reference
+ * src/models/DNABERT2/bert_layers.py:495-510, :881-1009), csrc/cls_head.hip:
+ *   t = tanh(x Wp^T + bp)   a = dropout(t; p, seed, offset)   logits = a Wc^T + bc
+ * x: B rows of H, DNA_F32 or DNA_BF16, row b at x + b * x_row_stride elements (the [CLS] rows of
+ * a [b*S, H] activation in place: stride S*H; a compact [B, H]: stride H). Wp [H, H], bp [H],
+ * Wc [C, H], bc [C]: the fp32 parameters. t, a [B, H] and logits [B, C] fp32. fp32 accumulation in
+ * a fixed order: bit-identical from run to run. H % 64 == 0, 1 <= C <= 64,
+ * 1 <= B <= DNA_CLS_MAX_BATCH (the pooler's grid: 8 rows per workgroup, 65,535 workgroup rows).
+ * The dropout draws follow dna_ln_fwd's (element b*H + j: Philox group (b*H + j) / 4 + offset).
+ * problem_type (bert_layers.py:986-998): regression = MSE mean over B*C (labels fp32 [B, C]; C = 1
+ * is the reference's squeeze), single-label = mean cross entropy (labels int64 [B] in [0, C)),
+ * multi-label = BCE-with-logits mean over B*C (labels fp32 [B, C]). loss: one float; dlogits
+ * [B, C]: d loss / d logits for a unit upstream gradient; pred [B] int64 (single-label only, may
+ * be NULL): argmax, a tie resolved to the lowest index.
+ * dna_cls_head_fwd: two launches; with labels != NULL the second also computes the loss (loss,
+ * dlogits, pred as dna_cls_loss), with labels == NULL those arguments are ignored.
+ * dna_cls_loss: the loss alone on given logits, one launch.
+ * dna_cls_head_bwd: from dlogits (times upstream[0], a device scalar, when upstream != NULL):
+ * dWc [C, H], dbc [C], dWp [H, H], dbp [H] (accumulate != 0: added into the buffers, e.g. the
+ * parameters' slices of a flat fp32 gradient) and dx [B, H] fp32 (always written). Two launches. */
+#define DNA_CLS_MAX_BATCH (8 * 65535)
+enum dna_cls_problem { DNA_CLS_REGRESSION = 0, DNA_CLS_SINGLE_LABEL = 1, DNA_CLS_MULTI_LABEL = 2 };
+size_t dna_cls_head_fwd_workspace(int batch, int hidden, int labels);
+int dna_cls_head_fwd(const void* x, int x_dtype, int64_t x_row_stride, const float* Wp,
+                     const float* bp, const float* Wc, const float* bc, int batch, int hidden,
+                     int labels_n, float p_drop, uint64_t seed, uint64_t offset, float* t, float* a,
+                     float* logits, const void* labels, int problem_type, float* loss,
+                     float* dlogits, int64_t* pred, void* workspace, size_t workspace_bytes,
+                     void* stream);
+int dna_cls_loss(const float* logits, const void* labels, int problem_type, int batch, int labels_n,
+                 float* loss, float* dlogits, int64_t* pred, void* stream);
+size_t dna_cls_head_bwd_workspace(int batch, int hidden, int labels);
+int dna_cls_head_bwd(const float* dlogits, const float* upstream, const void* x, int x_dtype,
+                     int64_t x_row_stride, const float* t, const float* a, const float* Wp,
+                     const float* Wc, int batch, int hidden, int labels_n, float p_drop,
+                     uint64_t seed, uint64_t offset, float* dWc, float* dbc, float* dWp, float* dbp,
+                     float* dx, int accumulate, void* workspace, size_t workspace_bytes,
+                     void* stream);
+
 /* ------------------------------------------------------------------ optimizer (flat buffers)
  * Lightning gradient_clip_val=1.0 (torch.nn.utils.clip_grad_norm_) + torch AdamW
  * (train.py:462-542, registry.optimizer["adamw"]) over ONE flat fp32 parameter buffer.
