@@ -570,6 +570,27 @@ inline int bwd_blocks(int rows, int cols) {
   return nb < lim ? nb : lim;
 }
 
+// Conditioning of the from-y backward for `npairs` LayerNorms whose gamma / beta lie in one
+// buffer (dna_ln_from_y_check): one block per pair, ok[pair] = every column passes.
+__global__ __launch_bounds__(256) void from_y_check_kernel(const float* __restrict__ base,
+                                                           const int64_t* __restrict__ goff,
+                                                           const int64_t* __restrict__ boff,
+                                                           const int* __restrict__ ncols,
+                                                           float max_ratio, float min_gamma,
+                                                           float margin, float shrink, int* ok) {
+  const float* gam = base + goff[blockIdx.x];
+  const float* bet = base + boff[blockIdx.x];
+  const int n = ncols[blockIdx.x];
+  int bad = 0;
+  for (int c = threadIdx.x; c < n; c += blockDim.x) {
+    const float g = fabsf(gam[c]) * (1.f - shrink) - margin;
+    const float b = fabsf(bet[c]) + margin;
+    bad |= !(g >= min_gamma && b <= max_ratio * g);  // a NaN fails
+  }
+  bad = __syncthreads_or(bad);
+  if (threadIdx.x == 0) ok[blockIdx.x] = !bad;
+}
+
 }  // namespace ln
 }  // namespace dna
 
@@ -642,8 +663,16 @@ extern "C" int dna_ln_bwd(const float* dy, const void* dy_bf16, const void* x, i
 // The same backward with x_hat recomputed from the forward's fp32 output, x_hat = (y - beta) /
 // gamma (act none only): it reads y instead of x and the residual -- one fp32 row instead of a
 // bf16 and an fp32 row (3.2 instead of 3.6 GB per DNABERT-2 call at T = 262,144) -- and neither
-// x nor the residual has to be kept for the backward. gamma must have no zero entries (those
-// columns' x_hat cannot be recovered; they are taken as 0).
+// x nor the residual has to be kept for the backward.
+// Contract: gamma has no zero entries (those columns' x_hat cannot be recovered: it is taken as
+// 0, which leaves their dgamma at 0 and drops their x_hat * c2 term from dx), and the pair is
+// well-conditioned. y carries an fp32 rounding of 2^-24 |y| <= 2^-24 (|beta| + |gamma| |x_hat|);
+// divided by gamma that is an x_hat error of about 2^-24 (|beta_k| / |gamma_k| + |x_hat|), so the
+// result is as accurate as dna_ln_bwd's only while max_k |beta_k| / |gamma_k| is small. Measured
+// against fp64 (1000 rows, 128 and 768 columns, beta = 1): at |beta / gamma| = 10 dgamma's error
+// is 1.2 to 2.6 times that of fp32 torch, like dna_ln_bwd's; at 100 it is 6.7 to 12.5 times, at
+// 10^6 up to 2.6e5 times. The caller decides (functional.ln_from_y_ok: ratio <= 16, |gamma| >=
+// 2^-64; dna_ln_from_y_check is the same test on the device); this entry point does not check.
 static int ln_bwd_from_y(const float* dy, const void* dy_bf16, const float* y, int x_dtype,
                          float p_drop, uint64_t seed, uint64_t offset, const float* gamma,
                          const float* beta, const float* rstd, int rows, int cols,
@@ -699,6 +728,23 @@ extern "C" int dna_ln_bwd_from_y_acc(const float* dy, const void* dy_bf16, const
   return ln_bwd_from_y(dy, dy_bf16, y, x_dtype, p_drop, seed, offset, gamma, beta, rstd, rows,
                        cols, dresidual, dx, dgamma, dbeta, dbias, workspace, workspace_bytes,
                        stream, 1);
+}
+
+// ok[i] = 1 where LayerNorm i (gamma at base + gamma_off[i], beta at base + beta_off[i], cols[i]
+// columns) may take the from-y backward and still may after its parameters have moved: every
+// column has g = |gamma| (1 - shrink) - margin >= min_gamma and |beta| + margin <= max_ratio * g.
+// One launch for all LayerNorms of a flat parameter buffer, after each optimizer step.
+extern "C" int dna_ln_from_y_check(const float* base, const int64_t* gamma_off,
+                                   const int64_t* beta_off, const int* cols, int npairs,
+                                   float max_ratio, float min_gamma, float margin, float shrink,
+                                   int* ok, void* stream) {
+  DNA_CHECK_ARG(npairs >= 0, "dna_ln_from_y_check: bad npairs");
+  if (npairs == 0) return DNA_OK;
+  DNA_CHECK_ARG(base && gamma_off && beta_off && cols && ok, "dna_ln_from_y_check: null pointer");
+  hipLaunchKernelGGL(from_y_check_kernel, dim3(npairs), dim3(256), 0, as_stream(stream), base,
+                     gamma_off, beta_off, cols, max_ratio, min_gamma, margin, shrink, ok);
+  DNA_LAUNCH_CHECK("dna_ln_from_y_check");
+  return DNA_OK;
 }
 
 // Pre-norm residual add + LayerNorm / RMSNorm (rms = 1: mamba_ssm's Block with fused_add_norm,

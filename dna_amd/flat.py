@@ -15,6 +15,21 @@ import torch
 
 ALIGN = 64  # elements (256 B fp32 / 128 B bf16): keeps every slice 16-B aligned for vector loads
 
+# Parameter writes torch cannot see: the fused AdamW step rewrites the flat buffer through raw
+# pointers and leaves every tensor's `_version` alone. FusedAdamW.step counts them here, so that
+# anything cached from parameter values (functional's LayerNorm backward verdicts) can tell that
+# it is out of date.
+_raw_writes = 0
+
+
+def note_raw_write():
+    global _raw_writes
+    _raw_writes += 1
+
+
+def raw_writes():
+    return _raw_writes
+
 
 class FlatParams:
     def __init__(self, module: torch.nn.Module, device=None, shadow_dtype=torch.bfloat16):

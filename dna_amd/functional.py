@@ -14,6 +14,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _native as N
+from .flat import raw_writes
 
 _DT = {torch.float32: N.F32, torch.bfloat16: N.BF16}
 
@@ -343,8 +344,10 @@ class FusedLayerNorm(torch.autograd.Function):
                    gamma.data_ptr(), beta.data_ptr(), n, d, eps, _p(y), _p(yb), mean.data_ptr(),
                    rstd.data_ptr(), N.stream_ptr())
         # backward from the fp32 output (x_hat = (y - beta) / gamma, dna_ln_bwd_from_y): one fp32
-        # row read instead of x + the residual, and neither is kept alive for the backward
-        ctx.from_y = y is not None and act == N.ACT_NONE and _LN_BWD_FROM_Y
+        # row read instead of x + the residual, and neither is kept alive for the backward --
+        # where (gamma, beta) leave it as accurate as the recomputation from x (ln_from_y_ok)
+        ctx.from_y = (y is not None and act == N.ACT_NONE and _LN_BWD_FROM_Y
+                      and any(ctx.needs_input_grad[:5]) and _ln_from_y_verdict(gamma, beta))
         if ctx.from_y:
             ctx.save_for_backward(y, bias, gamma, beta, rstd)
             ctx.shape = (n, d, x.dtype, residual is not None)
@@ -424,6 +427,139 @@ class FusedLayerNorm(torch.autograd.Function):
 # DNA_LN_BWD_FROM_Y=0: the LayerNorm backward recomputes x_hat from x (+ bias, dropout) + the
 # residual instead of from the fp32 output (A/B switch)
 _LN_BWD_FROM_Y = os.environ.get("DNA_LN_BWD_FROM_Y", "1") != "0"
+
+# Which (gamma, beta) may take the from-y backward. The forward's fp32 y carries a rounding of
+# 2^-24 |y| <= 2^-24 (|beta_k| + |gamma_k| |x_hat|); (y - beta) / gamma turns it into an x_hat
+# error of about 2^-24 (|beta_k| / |gamma_k| + |x_hat|), against 2^-24 |x_hat| for the
+# recomputation from x. So the from-y path is as accurate only while max_k |beta_k| / |gamma_k|
+# is small, and it needs every |gamma_k| > 0 (2^-64: y and 1 / gamma stay normal fp32 numbers).
+# Measured on the MI355X against fp64 (tests/test_gpu_layernorm_fp64.py (c): 1000 rows, 128 and
+# 768 columns, four columns at gamma = +-t, two of them with beta = 1; error of dgamma relative
+# to fp32 torch's error, 1.4e-7, over the four shapes; the recompute path stays at 1 to 2.5):
+#   |beta / gamma| = 10 (t = 1e-1): 1.2 .. 2.6      100 (t = 1e-2): 6.7 .. 12.5
+#   1e3: 44 .. 99       1e4: 335 .. 1010       1e6: 6.5e4 .. 2.6e5       gamma = 0: 3e6 .. 6e6
+# The tests allow 8. The error grows linearly in the ratio (about 0.11 per unit at worst), which
+# puts 16 at 3.3 or less: inside the bound with room to spare, 100 is outside it.
+LN_FROM_Y_MAX_RATIO = 16.0
+LN_FROM_Y_MIN_GAMMA = 2.0 ** -64
+
+
+def ln_from_y_ok(gamma, beta, margin=0.0, shrink=0.0):
+    """Whether a LayerNorm with these parameters may take the from-y backward: every column has
+    g = |gamma| (1 - shrink) - margin >= LN_FROM_Y_MIN_GAMMA and |beta| + margin <=
+    LN_FROM_Y_MAX_RATIO * g (NaN fails). margin / shrink: absolute / relative distance the
+    parameters may still move with the verdict standing (LNFromYGuard); 0 for the values as they
+    are. Pure function of the two tensors, on any device (one host read of the result)."""
+    g = gamma.detach().float().abs() * (1.0 - shrink) - margin
+    b = beta.detach().float().abs() + margin
+    return bool(((g >= LN_FROM_Y_MIN_GAMMA) & (b <= LN_FROM_Y_MAX_RATIO * g)).all())
+
+
+def _ln_from_y_verdict(gamma, beta):
+    """ln_from_y_ok(gamma, beta), cached on gamma as (ok, beta, gamma._version, beta._version,
+    last raw-write count it holds for). A hit costs no device work. A miss -- the first forward
+    of a pair, a direct caller's fresh tensors, an in-place change torch saw (load_state_dict), a
+    fused AdamW step with no LNFromYGuard refreshing the entry -- computes it with a host
+    synchronisation. The trainers keep the entries of their LayerNorms fresh (LNFromYGuard)."""
+    now = raw_writes()
+    c = getattr(gamma, "_dna_ln_verdict", None)
+    if (c is not None and c[1] is beta and c[2] == gamma._version and c[3] == beta._version
+            and c[4] >= now):
+        return c[0]
+    ok = ln_from_y_ok(gamma, beta)
+    gamma._dna_ln_verdict = (ok, beta, gamma._version, beta._version, now)
+    return ok
+
+
+class LNFromYGuard:
+    """Keeps the from-y verdicts of a FlatParams' LayerNorms fresh without a host synchronisation
+    in the training step. The fused AdamW step rewrites gamma and beta through raw pointers, so a
+    cached verdict would go stale unseen. After each optimizer step `launch()` runs one small
+    kernel over every (gamma, beta) pair a FusedLayerNorm has seen (dna_ln_from_y_check) and
+    copies the verdicts to pinned host memory, with an event; `poll()`, at the start of a step,
+    takes over whatever has arrived without blocking.
+
+    A verdict is computed MAX_AGE optimizer steps inside the accuracy threshold: AdamW moves a
+    parameter by at most lr * max(1, (1 - b1) / sqrt(1 - b2)) <= 3.2 lr per step (b = (0.9,
+    0.999)) plus lr * weight_decay * |p| of decay, so with margin = MAX_AGE * 3.2 * lr and
+    shrink = MAX_AGE * lr * weight_decay a verdict stays right for MAX_AGE steps and a stale one
+    cannot be wrong. poll() blocks only when the newest verdict taken over is older than that --
+    the host more than MAX_AGE steps ahead of the device."""
+
+    MAX_AGE = 16
+
+    def __init__(self, flat, opt):
+        self.flat, self.opt = flat, opt
+        self._pending = []  # (event, host verdicts, pairs with their versions, raw-write count)
+        self._free = []     # pinned host buffers to reuse
+        self._key, self._dev = None, None
+        self._good_until = -1
+
+    def _pairs(self):
+        out = []
+        for g in self.flat.params:
+            c = getattr(g, "_dna_ln_verdict", None)
+            if c is not None and id(c[1]) in self.flat._index:
+                out.append((g, c[1]))
+        return out
+
+    def launch(self):
+        """After the optimizer step, on its stream."""
+        pairs = self._pairs()
+        if not pairs or not self.flat.flat.is_cuda:
+            return
+        dev = self.flat.flat.device
+        key = tuple((id(g), id(b)) for g, b in pairs)
+        if key != self._key:
+            goff = [self.flat.slice_of(g)[0] for g, _ in pairs]
+            boff = [self.flat.slice_of(b)[0] for _, b in pairs]
+            cols = [g.numel() for g, _ in pairs]
+            self._dev = (torch.tensor(goff, dtype=torch.int64, device=dev),
+                         torch.tensor(boff, dtype=torch.int64, device=dev),
+                         torch.tensor(cols, dtype=torch.int32, device=dev),
+                         torch.empty(len(pairs), dtype=torch.int32, device=dev))
+            self._key, self._free = key, []
+        goff, boff, cols, ok = self._dev
+        g0 = self.opt.param_groups[0]
+        lr = max(float(g0["lr"]), float(g0.get("initial_lr", 0.0)))
+        b1, b2 = g0["betas"]
+        per_step = max(3.2, (1.0 - b1) / math.sqrt(1.0 - b2))
+        N.call("dna_ln_from_y_check", self.flat.flat.data_ptr(), goff.data_ptr(), boff.data_ptr(),
+               cols.data_ptr(), len(pairs), LN_FROM_Y_MAX_RATIO, LN_FROM_Y_MIN_GAMMA,
+               self.MAX_AGE * per_step * lr, self.MAX_AGE * lr * float(g0["weight_decay"]),
+               ok.data_ptr(), N.stream_ptr(dev))
+        host = self._free.pop() if self._free else torch.empty(len(pairs), dtype=torch.int32,
+                                                               pin_memory=True)
+        host.copy_(ok, non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record()
+        self._pending.append((ev, host, [(g, b, g._version, b._version) for g, b in pairs],
+                              raw_writes()))
+
+    def _take(self, item):
+        _, host, pairs, at = item
+        for (g, b, gv, bv), ok in zip(pairs, host.tolist()):
+            if g._version == gv and b._version == bv:  # else: changed since, the forward recomputes
+                g._dna_ln_verdict = (bool(ok), b, gv, bv, at + self.MAX_AGE)
+        self._good_until = at + self.MAX_AGE
+        if len(host) == len(self._key or ()):
+            self._free.append(host)
+
+    def poll(self):
+        """Before a step's forward: take over every finished check; wait for one only if the
+        verdicts held have run out."""
+        now = raw_writes()
+        while self._pending and self._pending[0][0].query():
+            self._take(self._pending.pop(0))
+        if self._good_until >= now:
+            return
+        for i, item in enumerate(self._pending):
+            if item[3] + self.MAX_AGE >= now:
+                item[0].synchronize()
+                for it in self._pending[:i + 1]:
+                    self._take(it)
+                del self._pending[:i + 1]
+                return
 
 
 class AddLayerNorm(torch.autograd.Function):

@@ -15,6 +15,7 @@ import math
 import torch
 
 from . import _native as N
+from .flat import note_raw_write
 
 
 class FusedAdamW:
@@ -52,6 +53,7 @@ class FusedAdamW:
                g["betas"][0], g["betas"][1], g["eps"], g["weight_decay"], self.step_count,
                self._sumsq.data_ptr() if clip else None,
                float(self.max_grad_norm or 0.0), float(grad_scale), N.stream_ptr())
+        note_raw_write()  # the parameters changed behind torch's version counters
         self.flat.refresh_transposed()
 
     def zero_grad(self, set_to_none=False):

@@ -16,6 +16,7 @@ import torch.distributed as dist
 from .bert_layers import BertForMaskedLM, BertForSequenceClassification, MLMIndex
 from .ddp import GradBucketReducer, broadcast_
 from .flat import FlatParams
+from .functional import LNFromYGuard
 from .optim import FusedAdamW, LinearLRSchedulerWarmup
 
 
@@ -82,6 +83,7 @@ class ModuleTrainer:
         self.flat.enable_direct_grad(True)
         self.opt = FusedAdamW(self.flat, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay,
                               max_grad_norm=max_grad_norm)
+        self.ln_guard = LNFromYGuard(self.flat, self.opt)
         self.reducer = GradBucketReducer(self.flat, bucket_mb=bucket_mb, wire_dtype=wire_dtype)
         self.world = self.reducer.world
         if self.reducer.enabled:  # DDP construction broadcast
@@ -91,6 +93,7 @@ class ModuleTrainer:
 
     def step(self, batch) -> torch.Tensor:
         self._versions = _sync_shadow(self.flat, self._versions)
+        self.ln_guard.poll()
         self.opt.zero_grad()
         self.reducer.prepare(sync=True)
         if self.autocast is not None:
@@ -101,6 +104,7 @@ class ModuleTrainer:
         loss.backward()
         self.reducer.finish()
         self.opt.step(grad_scale=self.reducer.grad_scale)
+        self.ln_guard.launch()
         self.global_step += 1
         return loss.detach()
 
@@ -115,6 +119,7 @@ class MLMTrainer:
         self.flat.enable_direct_grad(True)
         self.opt = FusedAdamW(self.flat, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay,
                               max_grad_norm=max_grad_norm)
+        self.ln_guard = LNFromYGuard(self.flat, self.opt)
         self.sched = None
         if scheduler is not None:
             self.sched = LinearLRSchedulerWarmup(self.opt, **scheduler)
@@ -148,6 +153,7 @@ class MLMTrainer:
         micro = batch if isinstance(batch, (list, tuple)) else [batch]
         div = len(micro) if accum is None else int(accum)
         self._versions = _sync_shadow(self.flat, self._versions)
+        self.ln_guard.poll()
         self.opt.zero_grad()
         total = None
         self.micro_losses = []
@@ -165,6 +171,7 @@ class MLMTrainer:
         self.opt.step(grad_scale=self.reducer.grad_scale)
         if self.sched is not None:
             self.sched.step()
+        self.ln_guard.launch()
         self.global_step += 1
         return total
 
@@ -197,6 +204,7 @@ class ClsTrainer:
         self.flat.enable_direct_grad(True)
         self.opt = FusedAdamW(self.flat, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay,
                               max_grad_norm=max_grad_norm)
+        self.ln_guard = LNFromYGuard(self.flat, self.opt)
         self.sched = LinearLRSchedulerWarmup(self.opt, **scheduler) if scheduler else None
         base = self.model.dropout_rng.seed if seed is None else int(seed) + 0x5EED
         self.model.dropout_rng.seed = (base * 1000003) & (2 ** 63 - 1)
@@ -217,12 +225,14 @@ class ClsTrainer:
         """One optimizer step on one batch (ids [b, S] and labels on the device). The logits and
         (single-label) predictions of the step stay in last_logits / last_pred; no host sync."""
         self._versions = _sync_shadow(self.flat, self._versions)
+        self.ln_guard.poll()
         self.opt.zero_grad()
         logits, loss, pred = self.model.cls_logits(input_ids, labels)
         loss.backward()
         self.opt.step()
         if self.sched is not None:
             self.sched.step()
+        self.ln_guard.launch()
         self.global_step += 1
         self.last_logits, self.last_pred = logits.detach(), pred
         return loss.detach()

@@ -131,8 +131,14 @@ int dna_ln_bwd(const float* dy, const void* dy_bf16, const void* x, int x_dtype,
                int rows, int cols, float* dresidual, void* dx, float* dgamma, float* dbeta,
                float* dbias, void* workspace, size_t workspace_bytes, void* stream);
 /* Backward of dna_ln_fwd (act none) with x_hat recomputed from the forward's fp32 output y:
- * x_hat = (y - beta) / gamma (gamma without zero entries; mean not needed) -- reads y instead of
- * x and the residual. Same outputs and workspace as dna_ln_bwd. */
+ * x_hat = (y - beta) / gamma (mean not needed) -- reads y instead of x and the residual. Same
+ * outputs and workspace as dna_ln_bwd.
+ * Contract (not checked here): gamma has no zero entry -- such a column's x_hat is taken as 0, so
+ * its dgamma comes out 0 and dx misses its term -- and max_k |beta_k| / |gamma_k| is small: y's
+ * fp32 rounding reaches x_hat as 2^-24 (|beta_k| / |gamma_k| + |x_hat|). Up to a ratio of 16 the
+ * result is as accurate as dna_ln_bwd's (measured at 10: dgamma within 2.6 times fp32 torch's
+ * error against fp64; at 100: up to 12.5 times). Callers test the pair first (dna_ln_from_y_check,
+ * dna_amd.functional.ln_from_y_ok) and call dna_ln_bwd where it fails. */
 int dna_ln_bwd_from_y(const float* dy, const void* dy_bf16, const float* y, int x_dtype,
                       float p_drop, uint64_t seed, uint64_t offset, const float* gamma,
                       const float* beta, const float* rstd, int rows, int cols, float* dresidual,
@@ -146,6 +152,14 @@ int dna_ln_bwd_from_y_acc(const float* dy, const void* dy_bf16, const float* y, 
                           const float* beta, const float* rstd, int rows, int cols,
                           float* dresidual, void* dx, float* dgamma, float* dbeta, float* dbias,
                           void* workspace, size_t workspace_bytes, void* stream);
+/* The from-y contract tested on the device for npairs LayerNorms whose parameters lie in one fp32
+ * buffer (gamma i at base + gamma_off[i], beta i at base + beta_off[i], cols[i] columns; the
+ * three arrays in device memory): ok[i] (device int) = 1 where every column has
+ * g = |gamma| (1 - shrink) - margin >= min_gamma and |beta| + margin <= max_ratio * g.
+ * margin / shrink: how far the parameters may move before the verdict is replaced. */
+int dna_ln_from_y_check(const float* base, const int64_t* gamma_off, const int64_t* beta_off,
+                        const int* cols, int npairs, float max_ratio, float min_gamma,
+                        float margin, float shrink, int* ok, void* stream);
 
 /* Pre-norm residual add + LayerNorm: sum = x + residual (fp32, written), y = LN(sum).
  * Replaces the flash_attn Block's `residual = dropout(x) + residual; norm(residual)` with
