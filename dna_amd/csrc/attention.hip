@@ -3,20 +3,35 @@
 // Replaces bert_layers.py:160-196 (PyTorch attention with an fp32 [b,H,S,S] bias built at
 // :421-448) and the disabled Triton slot flash_attn_triton.py:1077-1130. Scores never leave the
 // CU: S = Q K^T * scale + bias with bias[h,i,j] = -slope_h*|i-j| + (key j is pad ? -10000 : 0)
-// computed in registers, online softmax in log2 domain, P V on MFMA.
+// computed in registers, online softmax in log2 domain, P V on MFMA. No atomics anywhere: every
+// result is deterministic.
 //
-// bf16 path (head_dim 64): MFMA v_mfma_f32_32x32x16_bf16. A workgroup = 4 waves = 128 queries
-// of one (batch, head); each wave owns 32 queries and sweeps the keys in tiles of 64 staged in
-// LDS (K XOR-swizzled for conflict-free ds_read_b128 row reads; V read transposed with
-// ds_read_b64_tr_b16). The "swapped" products keep the query on the MFMA lane:
+// bf16 kernels (head_dim 64, seqlen a multiple of 64): MFMA v_mfma_f32_32x32x16_bf16 on 64-row
+// tiles staged in LDS (XOR-swizzled for conflict-free ds_read_b128 row reads; transposed operands
+// read with ds_read_b64_tr_b16). The "swapped" products keep the query on the MFMA lane:
 //   S^T[key][q] = K . Q^T       (A = K rows from LDS, B = Q held in registers)
 //   O^T[d][q]  += V^T . P^T     (A = V^T via tr reads, B = P^T straight from the accumulator)
 // so the softmax statistics of a query live in one lane pair (lane, lane^32).
-// Backward: dQ kernel (queries on lanes, like forward) and dK/dV kernel (keys on lanes, sweeping
-// query tiles), both recomputing P from the forward LSE -- no atomics, deterministic.
 //
-// fp32 path: exact-arithmetic reference-grade kernels (one thread per query / key) used for the
-// 1e-3 fp32 parity mode; not a throughput path.
+// What is in this file, and which shapes go where (the dispatch is at the end):
+//  * forward, fwd2_bf16_kernel<DMA>: 4 waves x 64 queries per workgroup, sweeping the keys.
+//      <true>   K/V tiles by LDS-DMA into a ring of three buffers: every S whose ring and pad-bias
+//               row fit 96 KiB of LDS (S <= 12288);
+//      <false>  K/V tiles staged through registers, double-buffered: longer S, or DNA_ATTN_FWD=2.
+//  * fused backward, one workgroup per (batch, head), dQ, dK and dV in one pass:
+//      bwd3_bf16_kernel<KB>    4 waves, S = 128*KB: S = 128 and 256 (and 512 on request);
+//      bwd3w8_bf16_kernel<KB>  8 waves, S = 256*KB: S = 512 (and 256 on request).
+//    "On request": DNA_ATTN_BWD3_NW=4|8, or the nw argument of dna_attn_bwd_var.
+//  * backward pair, dq2_bf16_kernel<NW> (queries on lanes, also writes delta) then
+//    dkdv2_bf16_kernel<NW> (keys on lanes), both recomputing P from the forward LSE: every other
+//    S, or all of them under DNA_ATTN_BWD=2.
+//      <8>  256 queries / keys per workgroup: S a multiple of 256 (unless DNA_ATTN_BWD_NW=4);
+//      <4>  128 per workgroup: the rest.
+//    Every backward kernel can also emit the column sums of dqkv (the QKV projection's bias
+//    gradient) as one partial row per 128 rows.
+//  * fp32, fwd_f32_kernel / delta_kernel + dq_f32_kernel + dkdv_f32_kernel: exact-arithmetic
+//    reference-grade kernels (one thread per query / key, any S) for the 1e-3 fp32 parity mode;
+//    not a throughput path.
 #include <stdlib.h>
 
 #include <algorithm>
@@ -28,13 +43,12 @@ namespace dna {
 namespace attn {
 
 constexpr int D = 64;       // head dim
-constexpr int BQ = 128;     // queries per workgroup (4 waves x 32)
+constexpr int BQ = 128;     // rows per 4-wave backward workgroup and per bias-gradient partial row
 constexpr int BK = 64;      // keys per LDS tile
 constexpr float LOG2E = 1.4426950408889634f;
 constexpr float LN2 = 0.6931471805599453f;
 constexpr float PAD_BIAS = -10000.0f;  // bert_layers.py:424
 
-typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4;
 typedef __attribute__((ext_vector_type(4))) short s16x4;
 
 // element offset of (row, col) in a [64][64] bf16 tile (128-B rows) with 16-byte chunks
@@ -66,20 +80,9 @@ __device__ __forceinline__ f32x16 mfma(bf16x8 a, bf16x8 b, f32x16 c) {
   return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
 }
 
-// key index (within a 32-row block) held by accumulator register r of lane half hh
-__device__ __forceinline__ int acc_row(int r, int hh) { return (r & 3) + 8 * (r >> 2) + 4 * hh; }
-
 // raw v_exp_f32 (2^x): arguments here are <= ~0 (scores minus their running max / LSE), where
 // the denormal-range fixups of exp2f() are not needed.
 __device__ __forceinline__ float ex2(float x) { return __builtin_amdgcn_exp2f(x); }
-
-// ALiBi distance term of accumulator register r (key offset within a 64-key tile, lane half hh)
-// in log2 units: slope2 * ((r&3) + 8*(r>>2) + 32*kh) + slope2*4*hh  -- one FMA.
-template <int KH, int R>
-__device__ __forceinline__ float alibi_b(float slope2, float h4) {
-  return fmaf(slope2, (float)(KH * 32 + (R & 3) + 8 * (R >> 2)), h4);
-}
-
 
 // Block -> (tile, head, batch). Blocks are dealt round-robin over the 8 XCDs (each with its own
 // L2); all tiles of one (batch, head) read the same K/V (or Q/dO) rows, so map them to blocks with
@@ -101,206 +104,9 @@ __device__ __forceinline__ void decode_block(int ntile, int H, int& tile, int& h
 }
 
 // ----------------------------------------------------------------------------- bf16 forward
-struct TileRegs {
-  bf16x8 k[2], v[2];
-};
-
-__global__ __launch_bounds__(256) void fwd_bf16_kernel(const bf16* __restrict__ qkv,
-                                                        const uint8_t* __restrict__ key_valid,
-                                                        const float* __restrict__ slopes, int S,
-                                                        int H, float scale_log2,
-                                                        bf16* __restrict__ out,
-                                                        float* __restrict__ lse) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  bf16* Ks = reinterpret_cast<bf16*>(smem);            // [2][64*64] swizzled
-  bf16* Vs = Ks + 2 * BK * D;                           // [2][64*64] swizzled
-  float* kb = reinterpret_cast<float*>(Vs + 2 * BK * D);  // [2][64] pad bias (log2 units)
-
-  int qblk, h, b;
-  decode_block((S + BQ - 1) / BQ, H, qblk, h, b);
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const int ql = lane & 31, hh = lane >> 5;
-  const int ld = 3 * H * D;
-  const bf16* base = qkv + (size_t)b * S * ld;
-  const int q0 = qblk * BQ + wave * 32;
-  const int qi = q0 + ql;
-  const int qrow = min(qi, S - 1);
-  const float slope2 = slopes[h] * LOG2E;
-
-  bf16x8 qf[4];
-#pragma unroll
-  for (int s = 0; s < 4; ++s)
-    qf[s] = *reinterpret_cast<const bf16x8*>(base + (size_t)qrow * ld + h * D + 16 * s + 8 * hh);
-
-  // staging assignment: 512 16-byte chunks per K (and V) tile, 2 per thread
-  auto load_tile = [&](int kt, TileRegs& t, float& bias) {
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      int c = tid + i * 256, r = c >> 3, ch = c & 7;
-      const bf16* src = base + (size_t)(kt * BK + r) * ld + h * D + ch * 8;
-      t.k[i] = *reinterpret_cast<const bf16x8*>(src + H * D);
-      t.v[i] = *reinterpret_cast<const bf16x8*>(src + 2 * H * D);
-    }
-    bias = 0.f;
-    if (tid < BK && key_valid) bias = key_valid[(size_t)b * S + kt * BK + tid] ? 0.f : PAD_BIAS * LOG2E;
-  };
-  auto store_tile = [&](int buf, const TileRegs& t, float bias) {
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      int c = tid + i * 256, r = c >> 3, ch = c & 7;
-      *reinterpret_cast<bf16x8*>(Ks + buf * BK * D + swz(r, ch * 8)) = t.k[i];
-      *reinterpret_cast<bf16x8*>(Vs + buf * BK * D + swz(r, ch * 8)) = t.v[i];
-    }
-    if (tid < BK) kb[buf * BK + tid] = bias;
-  };
-
-  f32x16 oacc[2];
-#pragma unroll
-  for (int i = 0; i < 16; ++i) { oacc[0][i] = 0.f; oacc[1][i] = 0.f; }
-  float m = -INFINITY, l = 0.f;
-
-  const int nt = S / BK;
-  const int kt0 = (qblk * BQ / BK) % nt;  // diagonal tiles first: the max settles early
-  {
-    TileRegs t; float bias;
-    load_tile(kt0, t, bias);
-    store_tile(0, t, bias);
-  }
-  __syncthreads();
-
-  const float h4 = slope2 * 4.f * hh;
-  for (int it = 0; it < nt; ++it) {
-    const int kt = (kt0 + it) % nt;
-    const int buf = it & 1;
-    TileRegs nx; float nbias = 0.f;
-    if (it + 1 < nt) load_tile((kt0 + it + 1) % nt, nx, nbias);
-
-    const bf16* K = Ks + buf * BK * D;
-    const bf16* V = Vs + buf * BK * D;
-    const float* kbias = kb + buf * BK;
-
-    // S^T = K Q^T for the two 32-key halves
-    f32x16 sacc[2];
-#pragma unroll
-    for (int kh = 0; kh < 2; ++kh) {
-#pragma unroll
-      for (int i = 0; i < 16; ++i) sacc[kh][i] = 0.f;
-      const int r = kh * 32 + ql;
-#pragma unroll
-      for (int s = 0; s < 4; ++s) {
-        bf16x8 a = *reinterpret_cast<const bf16x8*>(K + swz(r, 16 * s + 8 * hh));
-        sacc[kh] = mfma(a, qf[s], sacc[kh]);
-      }
-    }
-    // scores in log2 units: x = s*scale*log2e + bias2. For a tile wholly left (right) of this
-    // wave's 32 queries and without pads, bias2 = +-slope2*(key offset) + u with a per-lane u:
-    // x~ = fma(s, c, +-b_r) and u folds into the running max (2 VALU per score instead of 5).
-    float tmax = -INFINITY, u = 0.f;
-    const int kbase = kt * BK;
-    const bool haspad = key_valid && __any(kbias[lane] != 0.f);
-    const bool left = !haspad && kbase + BK - 1 < q0;
-    const bool right = !haspad && kbase > q0 + 31;
-    if (left || right) {
-      u = left ? slope2 * (float)(kbase - qi) : slope2 * (float)(qi - kbase);
-#define DNA_SEP(KH, R, SG)                                                   \
-  {                                                                         \
-    float x = fmaf(sacc[KH][R], scale_log2, SG alibi_b<KH, R>(slope2, h4));  \
-    sacc[KH][R] = x;                                                        \
-    tmax = fmaxf(tmax, x);                                                  \
-  }
-#define DNA_SEP16(KH, SG)                                                                     \
-  DNA_SEP(KH, 0, SG) DNA_SEP(KH, 1, SG) DNA_SEP(KH, 2, SG) DNA_SEP(KH, 3, SG)                 \
-  DNA_SEP(KH, 4, SG) DNA_SEP(KH, 5, SG) DNA_SEP(KH, 6, SG) DNA_SEP(KH, 7, SG)                 \
-  DNA_SEP(KH, 8, SG) DNA_SEP(KH, 9, SG) DNA_SEP(KH, 10, SG) DNA_SEP(KH, 11, SG)               \
-  DNA_SEP(KH, 12, SG) DNA_SEP(KH, 13, SG) DNA_SEP(KH, 14, SG) DNA_SEP(KH, 15, SG)
-      if (left) {
-        DNA_SEP16(0, +)
-        DNA_SEP16(1, +)
-      } else {
-        DNA_SEP16(0, -)
-        DNA_SEP16(1, -)
-      }
-#undef DNA_SEP16
-#undef DNA_SEP
-    } else {
-#pragma unroll
-      for (int kh = 0; kh < 2; ++kh) {
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          const int kr = kh * 32 + 8 * g + 4 * hh;  // first of 4 consecutive keys
-          const f32x4 pb = *reinterpret_cast<const f32x4*>(kbias + kr);
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            const int r = 4 * g + e;
-            const float rel = fabsf((float)(qi - (kbase + kr + e)));
-            float x = fmaf(sacc[kh][r], scale_log2, fmaf(-slope2, rel, pb[e]));
-            sacc[kh][r] = x;
-            tmax = fmaxf(tmax, x);
-          }
-        }
-      }
-    }
-    tmax = fmaxf(tmax, __shfl_xor(tmax, 32, 64)) + u;
-    const float mnew = fmaxf(m, tmax);
-    const float alpha = ex2(m - mnew);
-    m = mnew;
-    const float mu = mnew - u;
-    float psum = 0.f;
-#pragma unroll
-    for (int kh = 0; kh < 2; ++kh)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        float p = ex2(sacc[kh][r] - mu);
-        sacc[kh][r] = p;
-        psum += p;
-      }
-    l = l * alpha + psum;
-    if (__any(alpha != 1.f)) {  // wave-uniform: skipped once the running max has settled
-#pragma unroll
-      for (int i = 0; i < 16; ++i) { oacc[0][i] *= alpha; oacc[1][i] *= alpha; }
-    }
-    // O^T += V^T P^T
-    const int g16 = lane >> 4, i16 = lane & 15;
-#pragma unroll
-    for (int kh = 0; kh < 2; ++kh) {
-#pragma unroll
-      for (int s = 0; s < 2; ++s) {
-        bf16x8 pbf;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) pbf[j] = (bf16)sacc[kh][8 * s + j];
-        const int krow = kh * 32 + 16 * s + 4 * (g16 >> 1) + (i16 >> 2);
-#pragma unroll
-        for (int dt = 0; dt < 2; ++dt) {
-          const int dcol = 32 * dt + 16 * (g16 & 1) + 4 * (i16 & 3);
-          bf16x8 a = cat(tr_read(V + swz(krow, dcol)), tr_read(V + swz(krow + 8, dcol)));
-          oacc[dt] = mfma(a, pbf, oacc[dt]);
-        }
-      }
-    }
-    if (it + 1 < nt) store_tile(buf ^ 1, nx, nbias);
-    __syncthreads();
-  }
-
-  const float ltot = l + __shfl_xor(l, 32, 64);
-  const float inv = 1.f / ltot;
-  if (qi < S) {
-    bf16* orow = out + ((size_t)b * S + qi) * (H * D) + h * D;
-#pragma unroll
-    for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        bf16x4 v;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = (bf16)(oacc[dt][4 * g + e] * inv);
-        *reinterpret_cast<bf16x4*>(orow + 32 * dt + 8 * g + 4 * hh) = v;
-      }
-    if (hh == 0) lse[((size_t)b * H + h) * S + qi] = (m + __log2f(ltot)) * LN2;
-  }
-}
-
-// ----------------------------------------------------------------------------- bf16 forward, v2
-// Same math as fwd_bf16_kernel, reorganised for issue rate (the v1 loop was VALU-issue bound on
-// per-score bias arithmetic and per-tile address recomputation):
+// Online softmax over 64-key tiles, organised for issue rate (a first version, one 32-query block
+// per wave with the bias computed per score, was VALU-issue bound on that arithmetic and on
+// per-tile address recomputation):
 //  * a wave owns 64 queries = two 32-query blocks, so every K row read and V transposed read
 //    from LDS feeds two MFMAs; a workgroup (4 waves) owns 256 queries of one (batch, head);
 //  * ALiBi enters the MFMA as the initial accumulator: for a 32-key half that lies wholly left
@@ -335,24 +141,28 @@ __device__ __forceinline__ bool wave_any(bool p) { return __builtin_amdgcn_ballo
 // key offset (within a 32-key half, lane half hh excluded) of accumulator register r
 __device__ __forceinline__ constexpr int aoff(int r) { return (r & 3) + 8 * (r >> 2); }
 
-// NW waves per workgroup: 4 (two workgroups per CU) or 8 (one workgroup covers 512 queries, so
-// at S = 512 each (b, h)'s K/V tiles stream from HBM once instead of once per 256 queries)
-// DMA (NW = 4 only): the K / V tiles go global -> LDS by LDS-DMA (buffer_load ... lds) into a
-// ring of NST tile buffers, two tiles ahead of the one computed -- no staging registers, no LDS
-// writes by the waves, and a tile's HBM latency has two iterations to land; the pad bias of the
-// whole key row is staged in LDS once. LDS image as before (the swizzle is applied by choosing
-// which 16-B chunk of its row each lane fetches).
+// DMA: the K / V tiles go global -> LDS by LDS-DMA (buffer_load ... lds) into a ring of NST tile
+// buffers, two tiles ahead of the one computed -- no staging registers, no LDS writes by the
+// waves, and a tile's HBM latency has two iterations to land; the pad bias of the whole key row
+// is staged in LDS once. !DMA: each thread loads its chunks of the next tile into registers
+// (TileRegs) before the current tile's math and writes them to the other of two buffers after it.
+// Same LDS image either way (the DMA applies the swizzle by choosing which 16-B chunk of its row
+// each lane fetches).
 constexpr int NST = 3;
 constexpr size_t fwd_dma_lds(int S) { return (size_t)NST * 2 * BK * D * 2 + (size_t)S * 4; }
 
-template <int NQB, int NW = 4, bool DMA = false>
-__global__ __launch_bounds__(64 * NW, NQB == 1 ? 3 : (NQB == 2 ? 2 : 1)) void fwd2_bf16_kernel(const bf16* __restrict__ qkv,
+struct TileRegs {
+  bf16x8 k[2], v[2];
+};
+
+template <bool DMA>
+__global__ __launch_bounds__(256, 2) void fwd2_bf16_kernel(const bf16* __restrict__ qkv,
                                                            const uint8_t* __restrict__ key_valid,
                                                            const float* __restrict__ slopes,
                                                            int S, int H, float c,
                                                            bf16* __restrict__ out,
                                                            float* __restrict__ lse) {
-  static_assert(!DMA || NW == 4, "DMA staging: 4 waves");
+  constexpr int NQB = 2, NW = 4;  // 32-query blocks per wave, waves per workgroup
   extern __shared__ __attribute__((aligned(16))) char smem[];
   bf16* Ks = reinterpret_cast<bf16*>(smem);               // [2][64*64] swizzled
   bf16* Vs = Ks + 2 * BK * D;                             // [2][64*64] swizzled
@@ -466,7 +276,7 @@ __global__ __launch_bounds__(64 * NW, NQB == 1 ? 3 : (NQB == 2 ? 2 : 1)) void fw
   for (int j = 0; j < NQB; ++j) { m[j] = -INFINITY; l[j] = 0.f; }
 
   const int nt = S / BK;
-  const int kt0 = (qblk * (QPB / BK) + (NQB == 1 ? 0 : 1)) % nt;  // near-diagonal tiles first
+  const int kt0 = (qblk * (QPB / BK) + 1) % nt;  // near-diagonal tiles first
   auto tile_at = [&](int i) { const int t = kt0 + i % nt; return t >= nt ? t - nt : t; };
   if constexpr (DMA) {
     // the Q and key_valid loads are older than the tile pieces, so the first wait retires them
@@ -644,19 +454,18 @@ __global__ void delta_kernel(const T* __restrict__ out, const T* __restrict__ do
   delta[((size_t)b * H + h) * S + s] = acc;
 }
 
-// ----------------------------------------------------------------------------- bf16 dQ
-// Queries on lanes (as forward). Per 64-key tile: S^T (8 MFMA), dP^T = V dO^T (8), dQ^T += K^T dS^T (8).
+// ----------------------------------------------------------------------------- bias-gradient column sums
 // Column sums over a block's 128 rows of a [128 x 64] fp32 tile held as two 32x32 MFMA
 // accumulators (lane (wave, ql, hh): row wave*32+ql, columns 32dt + 8g + 4hh + e of acc[dt][4g+e]),
 // times `mul`; rows with !valid count as zero. `red` is >= 32 KiB of free LDS (16-B chunks
 // XOR-swizzled by row). Writes 64 floats to out. Fuses the packed-QKV projection's bias gradient
 // (column sums of dqkv) into the attention backward: one partial row per 128-row block.
-// Generalisation to NW waves (NW/4 groups of 4 waves = 128 rows): group g writes its 64 sums to
+// With NW waves (NW/4 groups of 4 waves = 128 rows), group g writes its 64 sums to
 // out + g * row_stride, so the partial-row layout stays one row per 128 rows whatever the block.
 // `red` needs NW * 32 * 64 floats.
 template <int NW>
-__device__ void block_colsum64_nw(float* red, const f32x16 (&acc)[2], float mul, bool valid,
-                                  float* __restrict__ out, size_t row_stride) {
+__device__ void block_colsum64(float* red, const f32x16 (&acc)[2], float mul, bool valid,
+                               float* __restrict__ out, size_t row_stride) {
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, ql = lane & 31, hh = lane >> 5;
   const int r = wave * 32 + ql;
 #pragma unroll
@@ -687,362 +496,13 @@ __device__ void block_colsum64_nw(float* red, const f32x16 (&acc)[2], float mul,
   __syncthreads();
 }
 
-__device__ void block_colsum64(float* red, const f32x16 (&acc)[2], float mul, bool valid,
-                               float* __restrict__ out) {
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, ql = lane & 31, hh = lane >> 5;
-  const int r = wave * 32 + ql;
-#pragma unroll
-  for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      f32x4 v;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) v[e] = valid ? acc[dt][4 * g + e] * mul : 0.f;
-      const int chunk = 8 * dt + 2 * g + hh;  // 16-B chunk of the 64-column row
-      *reinterpret_cast<f32x4*>(red + r * 64 + ((chunk ^ (r & 15)) << 2)) = v;
-    }
-  __syncthreads();
-  const int c = tid & 63, qr = tid >> 6;
-  float s = 0.f;
-#pragma unroll 8
-  for (int i = 0; i < 32; ++i) {
-    const int rr = qr * 32 + i;
-    s += red[rr * 64 + ((((c >> 2) ^ (rr & 15)) << 2) | (c & 3))];
-  }
-  __syncthreads();
-  red[qr * 64 + c] = s;
-  __syncthreads();
-  if (tid < 64) out[c] = (red[c] + red[64 + c]) + (red[128 + c] + red[192 + c]);
-  __syncthreads();
-}
-
-__global__ __launch_bounds__(256) void dq_bf16_kernel(
-    const bf16* __restrict__ qkv, const bf16* __restrict__ out, const bf16* __restrict__ dout,
-    const float* __restrict__ lse, float* __restrict__ delta,
-    const uint8_t* __restrict__ key_valid, const float* __restrict__ slopes, int S, int H,
-    float scale_log2, float scale, bf16* __restrict__ dqkv, float* __restrict__ dbias_part) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  bf16* Ks = reinterpret_cast<bf16*>(smem);     // [2][64*64] swizzled
-  bf16* Vs = Ks + 2 * BK * D;                    // [2][64*64] swizzled
-  float* kb = reinterpret_cast<float*>(Vs + 2 * BK * D);
-
-  int qblk, h, b;
-  decode_block((S + BQ - 1) / BQ, H, qblk, h, b);
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const int ql = lane & 31, hh = lane >> 5;
-  const int ld = 3 * H * D;
-  const bf16* base = qkv + (size_t)b * S * ld;
-  const int qi = qblk * BQ + wave * 32 + ql;
-  const int qrow = min(qi, S - 1);
-  const float slope2 = slopes[h] * LOG2E;
-  const float lse2 = lse[((size_t)b * H + h) * S + qrow] * LOG2E;
-
-  bf16x8 qf[4], df[4];
-  const size_t orow_off = ((size_t)b * S + qrow) * (H * D) + h * D;
-  float dl = 0.f;  // delta = rowsum(dO * O): this lane holds half the row, lane^32 the other
-#pragma unroll
-  for (int s = 0; s < 4; ++s) {
-    qf[s] = *reinterpret_cast<const bf16x8*>(base + (size_t)qrow * ld + h * D + 16 * s + 8 * hh);
-    df[s] = *reinterpret_cast<const bf16x8*>(dout + orow_off + 16 * s + 8 * hh);
-    const bf16x8 o8 = *reinterpret_cast<const bf16x8*>(out + orow_off + 16 * s + 8 * hh);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) dl = fmaf((float)df[s][j], (float)o8[j], dl);
-  }
-  dl += __shfl_xor(dl, 32, 64);
-  if (hh == 0 && qi < S) delta[((size_t)b * H + h) * S + qi] = dl;
-
-  auto load_tile = [&](int kt, TileRegs& t, float& bias) {
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      int c = tid + i * 256, r = c >> 3, ch = c & 7;
-      const bf16* src = base + (size_t)(kt * BK + r) * ld + h * D + ch * 8;
-      t.k[i] = *reinterpret_cast<const bf16x8*>(src + H * D);
-      t.v[i] = *reinterpret_cast<const bf16x8*>(src + 2 * H * D);
-    }
-    bias = 0.f;
-    if (tid < BK && key_valid) bias = key_valid[(size_t)b * S + kt * BK + tid] ? 0.f : PAD_BIAS * LOG2E;
-  };
-  auto store_tile = [&](int buf, const TileRegs& t, float bias) {
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      int c = tid + i * 256, r = c >> 3, ch = c & 7;
-      *reinterpret_cast<bf16x8*>(Ks + buf * BK * D + swz(r, ch * 8)) = t.k[i];
-      *reinterpret_cast<bf16x8*>(Vs + buf * BK * D + swz(r, ch * 8)) = t.v[i];
-    }
-    if (tid < BK) kb[buf * BK + tid] = bias;
-  };
-
-  f32x16 dq[2];
-#pragma unroll
-  for (int i = 0; i < 16; ++i) { dq[0][i] = 0.f; dq[1][i] = 0.f; }
-
-  const int nt = S / BK;
-  {
-    TileRegs t; float bias;
-    load_tile(0, t, bias);
-    store_tile(0, t, bias);
-  }
-  __syncthreads();
-  const int g16 = lane >> 4, i16 = lane & 15;
-
-  const int q0 = qblk * BQ + wave * 32;
-  const float h4 = slope2 * 4.f * hh;
-  for (int kt = 0; kt < nt; ++kt) {
-    const int buf = kt & 1;
-    TileRegs nx; float nbias = 0.f;
-    if (kt + 1 < nt) load_tile(kt + 1, nx, nbias);
-    const bf16* K = Ks + buf * BK * D;
-    const bf16* V = Vs + buf * BK * D;
-    const float* kbias = kb + buf * BK;
-    const int kbase = kt * BK;
-    // separable ALiBi (see the forward): tiles wholly left/right of this wave's queries, no pads
-    const bool haspad = key_valid && __any(kbias[lane] != 0.f);
-    const bool left = !haspad && kbase + BK - 1 < q0;
-    const bool right = !haspad && kbase > q0 + 31;
-    const float lu = lse2 - (left ? slope2 * (float)(kbase - qi) : slope2 * (float)(qi - kbase));
-
-#pragma unroll
-    for (int kh = 0; kh < 2; ++kh) {
-      f32x16 sa, pa;
-#pragma unroll
-      for (int i = 0; i < 16; ++i) { sa[i] = 0.f; pa[i] = 0.f; }
-      const int r = kh * 32 + ql;
-#pragma unroll
-      for (int s = 0; s < 4; ++s) {
-        bf16x8 ak = *reinterpret_cast<const bf16x8*>(K + swz(r, 16 * s + 8 * hh));
-        bf16x8 av = *reinterpret_cast<const bf16x8*>(V + swz(r, 16 * s + 8 * hh));
-        sa = mfma(ak, qf[s], sa);
-        pa = mfma(av, df[s], pa);
-      }
-      // dS^T = P^T (dP^T - delta), P^T = exp2(S c + bias - lse2)
-      if (left || right) {
-#pragma unroll
-        for (int rr = 0; rr < 16; ++rr) {
-          const float br = fmaf(slope2, (float)(kh * 32 + (rr & 3) + 8 * (rr >> 2)), h4);
-          const float x = fmaf(sa[rr], scale_log2, left ? br : -br);
-          sa[rr] = ex2(x - lu) * (pa[rr] - dl);
-        }
-      } else {
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          const int kr = kh * 32 + 8 * g + 4 * hh;
-          const f32x4 pb = *reinterpret_cast<const f32x4*>(kbias + kr);
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            const int rr = 4 * g + e;
-            const float rel = fabsf((float)(qi - (kbase + kr + e)));
-            float x = fmaf(sa[rr], scale_log2, fmaf(-slope2, rel, pb[e]));
-            float p = ex2(x - lse2);
-            sa[rr] = p * (pa[rr] - dl);
-          }
-        }
-      }
-      // dQ^T[d][q] += K^T[d][key] dS^T[key][q]   (k-steps over 16 keys)
-#pragma unroll
-      for (int s = 0; s < 2; ++s) {
-        bf16x8 db;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) db[j] = (bf16)sa[8 * s + j];
-        const int krow = kh * 32 + 16 * s + 4 * (g16 >> 1) + (i16 >> 2);
-#pragma unroll
-        for (int dt = 0; dt < 2; ++dt) {
-          const int dcol = 32 * dt + 16 * (g16 & 1) + 4 * (i16 & 3);
-          bf16x8 a = cat(tr_read(K + swz(krow, dcol)), tr_read(K + swz(krow + 8, dcol)));
-          dq[dt] = mfma(a, db, dq[dt]);
-        }
-      }
-    }
-    if (kt + 1 < nt) store_tile(buf ^ 1, nx, nbias);
-    __syncthreads();
-  }
-  if (qi < S) {
-    bf16* row = dqkv + ((size_t)b * S + qi) * ld + h * D;
-#pragma unroll
-    for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        bf16x4 v;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = (bf16)(dq[dt][4 * g + e] * scale);
-        *reinterpret_cast<bf16x4*>(row + 32 * dt + 8 * g + 4 * hh) = v;
-      }
-  }  if (dbias_part) {
-    const int nq = (S + BQ - 1) / BQ;
-    block_colsum64(reinterpret_cast<float*>(smem), dq, scale, qi < S,
-                   dbias_part + ((size_t)b * nq + qblk) * ld + h * D);
-  }
-}
-
-// ----------------------------------------------------------------------------- bf16 dK / dV
-// Keys on lanes: a workgroup = 4 waves x 32 keys; sweeps query tiles of 64 (two 32-halves).
-// Per 32-query half: S (4 MFMA), dP = dO V^T (4), dV^T += dO^T P (4), dK^T += Q^T dS (4).
-constexpr int BKW = 128;  // keys per workgroup
-constexpr int BQT = 64;   // queries per LDS tile
-
-__global__ __launch_bounds__(256) void dkdv_bf16_kernel(
-    const bf16* __restrict__ qkv, const bf16* __restrict__ dout, const float* __restrict__ lse,
-    const float* __restrict__ delta, const uint8_t* __restrict__ key_valid,
-    const float* __restrict__ slopes, int S, int H, float scale_log2, float scale,
-    bf16* __restrict__ dqkv, float* __restrict__ dbias_part) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  bf16* Qs = reinterpret_cast<bf16*>(smem);      // [2][64*64] swizzled
-  bf16* Os = Qs + 2 * BQT * D;                    // [2][64*64] dO, swizzled
-  float* ls = reinterpret_cast<float*>(Os + 2 * BQT * D);  // [2][64] lse (log2)
-  float* ds = ls + 2 * BQT;                                 // [2][64] delta
-
-  int kblk, h, b;
-  decode_block((S + BKW - 1) / BKW, H, kblk, h, b);
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const int kl = lane & 31, hh = lane >> 5;
-  const int ld = 3 * H * D;
-  const bf16* base = qkv + (size_t)b * S * ld;
-  const bf16* obase = dout + (size_t)b * S * (H * D);
-  const int kj = kblk * BKW + wave * 32 + kl;
-  const int krow = min(kj, S - 1);
-  const float slope2 = slopes[h] * LOG2E;
-  const float kbias = (key_valid && !key_valid[(size_t)b * S + krow]) ? PAD_BIAS * LOG2E : 0.f;
-  const float h4kv = slope2 * 4.f * hh;
-  const float* lse_bh = lse + ((size_t)b * H + h) * S;
-  const float* dl_bh = delta + ((size_t)b * H + h) * S;
-
-  bf16x8 kf[4], vf[4];
-#pragma unroll
-  for (int s = 0; s < 4; ++s) {
-    kf[s] = *reinterpret_cast<const bf16x8*>(base + (size_t)krow * ld + H * D + h * D + 16 * s + 8 * hh);
-    vf[s] = *reinterpret_cast<const bf16x8*>(base + (size_t)krow * ld + 2 * H * D + h * D + 16 * s + 8 * hh);
-  }
-
-  struct QRegs { bf16x8 q[2], o[2]; float l, d; };
-  auto load_tile = [&](int qt, QRegs& t) {
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      int c = tid + i * 256, r = c >> 3, ch = c & 7;
-      const size_t row = (size_t)(qt * BQT + r);
-      t.q[i] = *reinterpret_cast<const bf16x8*>(base + row * ld + h * D + ch * 8);
-      t.o[i] = *reinterpret_cast<const bf16x8*>(obase + row * (H * D) + h * D + ch * 8);
-    }
-    if (tid < BQT) { t.l = lse_bh[qt * BQT + tid] * LOG2E; t.d = dl_bh[qt * BQT + tid]; }
-  };
-  auto store_tile = [&](int buf, const QRegs& t) {
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      int c = tid + i * 256, r = c >> 3, ch = c & 7;
-      *reinterpret_cast<bf16x8*>(Qs + buf * BQT * D + swz(r, ch * 8)) = t.q[i];
-      *reinterpret_cast<bf16x8*>(Os + buf * BQT * D + swz(r, ch * 8)) = t.o[i];
-    }
-    if (tid < BQT) { ls[buf * BQT + tid] = t.l; ds[buf * BQT + tid] = t.d; }
-  };
-
-  f32x16 dk[2], dv[2];
-#pragma unroll
-  for (int i = 0; i < 16; ++i) { dk[0][i] = dk[1][i] = dv[0][i] = dv[1][i] = 0.f; }
-
-  const int nt = S / BQT;
-  {
-    QRegs t;
-    load_tile(0, t);
-    store_tile(0, t);
-  }
-  __syncthreads();
-  const int g16 = lane >> 4, i16 = lane & 15;
-
-  for (int qt = 0; qt < nt; ++qt) {
-    const int buf = qt & 1;
-    QRegs nx;
-    if (qt + 1 < nt) load_tile(qt + 1, nx);
-    const bf16* Q = Qs + buf * BQT * D;
-    const bf16* O = Os + buf * BQT * D;
-    const float* L = ls + buf * BQT;
-    const float* DL = ds + buf * BQT;
-    const int qbase = qt * BQT;
-    const int kw0 = kblk * BKW + wave * 32;
-#pragma unroll
-    for (int qh = 0; qh < 2; ++qh) {
-      const int qb = qbase + qh * 32;
-      const bool after = qb > kw0 + 31;   // every query of this half is right of every key
-      const bool before = qb + 31 < kw0;  // every query is left of every key
-      f32x16 sa, pa;
-#pragma unroll
-      for (int i = 0; i < 16; ++i) { sa[i] = 0.f; pa[i] = 0.f; }
-      const int r = qh * 32 + kl;  // A-operand row = query
-#pragma unroll
-      for (int s = 0; s < 4; ++s) {
-        bf16x8 aq = *reinterpret_cast<const bf16x8*>(Q + swz(r, 16 * s + 8 * hh));
-        bf16x8 ao = *reinterpret_cast<const bf16x8*>(O + swz(r, 16 * s + 8 * hh));
-        sa = mfma(aq, kf[s], sa);  // S[q][key]
-        pa = mfma(ao, vf[s], pa);  // dP[q][key]
-      }
-      f32x16 pp;
-      // after: bias2 = -slope2*(q - k) = -(slope2*c_r + h4 - u); before: +(slope2*c_r + h4 + u)
-      const float hu = after ? h4kv - slope2 * (float)(kj - qb) - kbias
-                             : h4kv + slope2 * (float)(qb - kj) + kbias;
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const int qr = qh * 32 + 8 * g + 4 * hh;
-        const f32x4 lq = *reinterpret_cast<const f32x4*>(L + qr);
-        const f32x4 dq4 = *reinterpret_cast<const f32x4*>(DL + qr);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const int rr = 4 * g + e;
-          float x;
-          if (after || before) {
-            const float br = fmaf(slope2, (float)(8 * g + e), hu);
-            x = fmaf(sa[rr], scale_log2, after ? -br : br);
-          } else {
-            const float rel = fabsf((float)(qbase + qr + e - kj));
-            x = fmaf(sa[rr], scale_log2, fmaf(-slope2, rel, kbias));
-          }
-          float p = ex2(x - lq[e]);
-          pp[rr] = p;
-          sa[rr] = p * (pa[rr] - dq4[e]);  // dS
-        }
-      }
-      // dV^T[d][key] += dO^T[d][q] P[q][key];  dK^T[d][key] += Q^T[d][q] dS[q][key]
-#pragma unroll
-      for (int s = 0; s < 2; ++s) {
-        bf16x8 pb, sb;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) { pb[j] = (bf16)pp[8 * s + j]; sb[j] = (bf16)sa[8 * s + j]; }
-        const int qrow = qh * 32 + 16 * s + 4 * (g16 >> 1) + (i16 >> 2);
-#pragma unroll
-        for (int dt = 0; dt < 2; ++dt) {
-          const int dcol = 32 * dt + 16 * (g16 & 1) + 4 * (i16 & 3);
-          bf16x8 ao = cat(tr_read(O + swz(qrow, dcol)), tr_read(O + swz(qrow + 8, dcol)));
-          bf16x8 aq = cat(tr_read(Q + swz(qrow, dcol)), tr_read(Q + swz(qrow + 8, dcol)));
-          dv[dt] = mfma(ao, pb, dv[dt]);
-          dk[dt] = mfma(aq, sb, dk[dt]);
-        }
-      }
-    }
-    if (qt + 1 < nt) store_tile(buf ^ 1, nx);
-    __syncthreads();
-  }
-  if (kj < S) {
-    bf16* row = dqkv + ((size_t)b * S + kj) * ld + h * D;
-#pragma unroll
-    for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        bf16x4 vk, vv;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          vk[e] = (bf16)(dk[dt][4 * g + e] * scale);
-          vv[e] = (bf16)dv[dt][4 * g + e];
-        }
-        *reinterpret_cast<bf16x4*>(row + H * D + 32 * dt + 8 * g + 4 * hh) = vk;
-        *reinterpret_cast<bf16x4*>(row + 2 * H * D + 32 * dt + 8 * g + 4 * hh) = vv;
-      }
-  }  if (dbias_part) {
-    const int nk = (S + BKW - 1) / BKW;
-    float* prow = dbias_part + ((size_t)b * nk + kblk) * ld + h * D;
-    block_colsum64(reinterpret_cast<float*>(smem), dk, scale, kj < S, prow + H * D);
-    block_colsum64(reinterpret_cast<float*>(smem), dv, 1.f, kj < S, prow + 2 * H * D);
-  }
-}
-
-// ----------------------------------------------------------------------------- bf16 backward, v2
-// Same decomposition as dq_bf16_kernel / dkdv_bf16_kernel (no atomics, deterministic) with the
-// per-score VALU work cut the way fwd2_bf16_kernel does it:
+// ----------------------------------------------------------------------------- bf16 backward, v2 pair
+// Two kernels, each recomputing P from the forward LSE (no atomics, deterministic):
+//  dQ     queries on lanes (as forward), NW waves x 32 queries per workgroup. Per 64-key tile:
+//         S^T (8 MFMA), dP^T = V dO^T (8), dQ^T += K^T dS^T (8);
+//  dK/dV  keys on lanes, NW waves x 32 keys per workgroup, sweeping query tiles of 64 (two
+//         32-halves). Per half: S (4 MFMA), dP = dO V^T (4), dV^T += dO^T P (4), dK^T += Q^T dS (4).
+// The per-score VALU work is cut the way fwd2_bf16_kernel does it:
 //  * row constants enter the MFMAs as initial accumulators. dK/dV kernel (queries on rows):
 //    S starts from (-LSE2 -+ slope2*q)/c, so with the per-lane (key) constant U = +-slope2*k +
 //    pad(k), P = exp2(S*c + U) is one FMA + v_exp; dP starts from -delta, so dS = P * dP.
@@ -1050,6 +510,9 @@ __global__ __launch_bounds__(256) void dkdv_bf16_kernel(
 //    separable block, dP^T from -delta;
 //  * blocks are classified per 32x32 (before / after / diagonal) with scalar branches; only
 //    diagonal blocks (and, in the dQ kernel, key tiles with pad keys) compute |q - k| per score.
+constexpr int BKW = 128;  // keys per 4-wave dK/dV workgroup, and per bias-gradient partial row
+constexpr int BQT = 64;   // queries per LDS tile
+
 template <int NW>
 __global__ __launch_bounds__(NW * 64, 8 / NW) void dkdv2_bf16_kernel(
     const bf16* __restrict__ qkv, const bf16* __restrict__ dout, const float* __restrict__ lse,
@@ -1220,15 +683,15 @@ __global__ __launch_bounds__(NW * 64, 8 / NW) void dkdv2_bf16_kernel(
   if (dbias_part) {  // partial rows are per 128 keys (dna_attn_dbias_part_rows)
     const int nk = (S + BKW - 1) / BKW;
     float* prow = dbias_part + ((size_t)b * nk + kblk * (NW / 4)) * ld + h * D;
-    block_colsum64_nw<NW>(reinterpret_cast<float*>(smem), dk, scale, kj < S, prow + H * D, ld);
-    block_colsum64_nw<NW>(reinterpret_cast<float*>(smem), dv, 1.f, kj < S, prow + 2 * H * D, ld);
+    block_colsum64<NW>(reinterpret_cast<float*>(smem), dk, scale, kj < S, prow + H * D, ld);
+    block_colsum64<NW>(reinterpret_cast<float*>(smem), dv, 1.f, kj < S, prow + 2 * H * D, ld);
   }
 }
 
 // dQ with queries on lanes: per 32-key half, S^T from the ALiBi vector of a separable block,
 // P = exp2(S c + U - LSE2), dS = P (dP - delta) with dP^T started from -delta,
 // dQ^T += K^T dS^T. Also writes delta for the dK/dV kernel and the fused bias-gradient column
-// partials (as dq_bf16_kernel).
+// partials.
 template <int NW>
 __global__ __launch_bounds__(NW * 64, 8 / NW) void dq2_bf16_kernel(
     const bf16* __restrict__ qkv, const bf16* __restrict__ out, const bf16* __restrict__ dout,
@@ -1400,8 +863,8 @@ __global__ __launch_bounds__(NW * 64, 8 / NW) void dq2_bf16_kernel(
   }
   if (dbias_part) {  // partial rows are per 128 queries (dna_attn_dbias_part_rows)
     const int nq = (S + BQ - 1) / BQ;
-    block_colsum64_nw<NW>(reinterpret_cast<float*>(smem), dq, scale, qi < S,
-                          dbias_part + ((size_t)b * nq + qblk * (NW / 4)) * ld + h * D, ld);
+    block_colsum64<NW>(reinterpret_cast<float*>(smem), dq, scale, qi < S,
+                       dbias_part + ((size_t)b * nq + qblk * (NW / 4)) * ld + h * D, ld);
   }
 }
 
@@ -1477,18 +940,14 @@ __device__ unsigned long long g_bwd3_stamps[8][17][6];  // [wave][slice][stamp];
 #else
 #define BWD3_STAMP(t, k) do {} while (0)
 #endif
-// V bit 0: fused bias-gradient column sums; bit 1: per-step sched_barriers in the pipelined
-// phase 1 (keeps the softmax tail between the previous block's dV/dK MFMAs; A/B via
-// DNA_ATTN_BWD3_SB)
-template <int KB, int V>
+// DB: fused bias-gradient column sums
+template <int KB, bool DB>
 __global__ __launch_bounds__(256, 1) void bwd3_bf16_kernel(
     const bf16* __restrict__ qkv, const bf16* __restrict__ out, const bf16* __restrict__ dout,
     const float* __restrict__ lse, const uint8_t* __restrict__ key_valid,
     const float* __restrict__ slopes, int H, float c, float scale, bf16* __restrict__ dqkv,
     float* __restrict__ dbias_part) {
-  constexpr bool DB = V & 1;  // fused bias-gradient column sums
   constexpr bool DBL = DB, DBE = DB;
-  constexpr bool PIPE_SB = (V & 2) != 0;
   constexpr int S = 128 * KB;   // keys = queries of one (batch, head)
   constexpr int KPW = 32 * KB;  // keys per wave
   constexpr int NS = S / 32;    // query slices
@@ -1715,7 +1174,6 @@ __global__ __launch_bounds__(256, 1) void bwd3_bf16_kernel(
             if (DBL) ssum += ds;
           }
         }
-        if (PIPE_SB) __builtin_amdgcn_sched_barrier(0);
       }
       if (kb > 0) {
         // dS^T image of block kb-1: register group g holds q = 8g + 4hh + 0..3 of key kl (the
@@ -2507,7 +1965,6 @@ __global__ __launch_bounds__(64) void dkdv_f32_kernel(const float* __restrict__ 
 }
 
 constexpr size_t FWD_LDS = 2 * (2 * BK * D * sizeof(bf16)) + 2 * BK * sizeof(float);
-constexpr size_t DKDV_LDS = 2 * (2 * BQT * D * sizeof(bf16)) + 4 * BQT * sizeof(float);
 constexpr size_t DKDV2_LDS = 2 * (2 * BQT * D * sizeof(bf16)) + 8 * BQT * sizeof(float);
 
 }  // namespace attn
@@ -2515,6 +1972,48 @@ constexpr size_t DKDV2_LDS = 2 * (2 * BQT * D * sizeof(bf16)) + 8 * BQT * sizeof
 
 using namespace dna;
 using namespace dna::attn;
+
+// ----------------------------------------------------------------------------- dispatch
+// Environment switches between the kernels above (benchmarks / A/B), each read once per process.
+// A value that selects nothing is an error, never a quiet fall-back to the default.
+struct EnvSwitch {
+  const char* name;
+  const char* accepted;  // for the error message
+  int value;             // -1: set to something not accepted
+};
+// dflt (also the value when unset or empty) and up to two alternatives are accepted
+static EnvSwitch env_switch(const char* name, const char* accepted, int dflt, int alt,
+                            int alt2 = -1) {
+  const char* v = getenv(name);
+  if (!v || !*v) return {name, accepted, dflt};
+  char* end;
+  const long x = strtol(v, &end, 10);
+  const bool ok = *end == 0 && x >= 0 && (x == dflt || x == alt || x == alt2);
+  return {name, accepted, ok ? (int)x : -1};
+}
+struct AttnEnv {
+  EnvSwitch fwd, bwd, bwd3_nw, bwd_nw;
+};
+static const AttnEnv& attn_env() {
+  static const AttnEnv e = {
+      // register-staged forward (2) in place of the LDS-DMA ring where that fits (0)
+      env_switch("DNA_ATTN_FWD", "0, 2 or unset", 0, 2),
+      // the fused backward where there is one (3), or the v2 pair at every length (2)
+      env_switch("DNA_ATTN_BWD", "2, 3 or unset", 3, 2),
+      // waves per workgroup of the fused backward at S = 256 / 512. Unset: 8 at S = 512 (attn_bwd
+      // 1.91 -> 1.71 ms per launch in the DNABERT-2 bench, b = 512, interleaved A/B in
+      // profiles/r07/ab_attn_bwd_8wave.txt), 4 at S = 256 (not measured in a training step)
+      env_switch("DNA_ATTN_BWD3_NW", "0, 4, 8 or unset", 0, 4, 8),
+      // waves per workgroup of the v2 pair where S is a multiple of 256
+      env_switch("DNA_ATTN_BWD_NW", "4, 8 or unset", 8, 4)};
+  return e;
+}
+
+static int check_env(const EnvSwitch& e, const char* fn) {
+  if (e.value >= 0) return DNA_OK;
+  set_error("%s: %s=%s selects no kernel (accepted: %s)", fn, e.name, getenv(e.name), e.accepted);
+  return DNA_ERR_UNSUPPORTED;
+}
 
 static int check_common(const void* qkv, const float* slopes, int batch, int seqlen, int heads,
                         int head_dim, int dtype, const char* fn) {
@@ -2541,43 +2040,24 @@ extern "C" int dna_attn_fwd(const void* qkv, const uint8_t* key_valid, const flo
   DNA_CHECK_ARG(out && lse, "dna_attn_fwd: null output");
   hipStream_t s = as_stream(stream);
   if (dtype == DNA_BF16) {
-    // A/B switch for benchmarks: DNA_ATTN_FWD=1 runs the v1 forward
-    static const int forced = getenv("DNA_ATTN_FWD") ? atoi(getenv("DNA_ATTN_FWD")) : 0;
-    if (forced == 1) {
-      dim3 grid(((seqlen + BQ - 1) / BQ) * heads * batch);
-      hipLaunchKernelGGL(fwd_bf16_kernel, grid, dim3(256), FWD_LDS, s, (const bf16*)qkv,
+    const EnvSwitch& env = attn_env().fwd;
+    if ((st = check_env(env, "dna_attn_fwd"))) return st;
+    const dim3 grid(((seqlen + BQ2 - 1) / BQ2) * heads * batch);
+    if (env.value != 2 && fwd_dma_lds(seqlen) <= 96 * 1024) {
+      // default: the LDS-DMA K/V ring (0.731 -> 0.712 ms at b = 512, interleaved A/B in
+      // profiles/r06/ab_attn_fwd_dma.txt)
+      static const bool attr = [] {
+        (void)hipFuncSetAttribute((const void*)fwd2_bf16_kernel<true>,
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
+        return true;
+      }();
+      (void)attr;
+      hipLaunchKernelGGL((fwd2_bf16_kernel<true>), grid, dim3(256), fwd_dma_lds(seqlen), s,
+                         (const bf16*)qkv, key_valid, slopes, seqlen, heads,
+                         softmax_scale * LOG2E, (bf16*)out, lse);
+    } else {  // the ring does not fit (S > 12288), or DNA_ATTN_FWD=2
+      hipLaunchKernelGGL((fwd2_bf16_kernel<false>), grid, dim3(256), FWD_LDS, s, (const bf16*)qkv,
                          key_valid, slopes, seqlen, heads, softmax_scale * LOG2E, (bf16*)out, lse);
-    } else {
-      if (forced == 4) {  // four 32-query blocks per wave, 1 wave per SIMD (A/B)
-        dim3 grid(((seqlen + 511) / 512) * heads * batch);
-        hipLaunchKernelGGL((fwd2_bf16_kernel<4>), grid, dim3(256), FWD_LDS, s, (const bf16*)qkv,
-                           key_valid, slopes, seqlen, heads, softmax_scale * LOG2E, (bf16*)out, lse);
-      } else if (forced == 3) {  // one 32-query block per wave, 3 waves per SIMD (A/B)
-        dim3 grid(((seqlen + 127) / 128) * heads * batch);
-        hipLaunchKernelGGL((fwd2_bf16_kernel<1>), grid, dim3(256), FWD_LDS, s, (const bf16*)qkv,
-                           key_valid, slopes, seqlen, heads, softmax_scale * LOG2E, (bf16*)out, lse);
-      } else if (forced != 2 && forced != 8 && fwd_dma_lds(seqlen) <= 96 * 1024) {
-        // default: the LDS-DMA K/V ring (0.731 -> 0.712 ms at b = 512, interleaved A/B in
-        // profiles/r06/ab_attn_fwd_dma.txt); DNA_ATTN_FWD=2 runs the register-staged form
-        static const bool attr = [] {
-          (void)hipFuncSetAttribute((const void*)fwd2_bf16_kernel<2, 4, true>,
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-          return true;
-        }();
-        (void)attr;
-        dim3 grid(((seqlen + BQ2 - 1) / BQ2) * heads * batch);
-        hipLaunchKernelGGL((fwd2_bf16_kernel<2, 4, true>), grid, dim3(256), fwd_dma_lds(seqlen), s,
-                           (const bf16*)qkv, key_valid, slopes, seqlen, heads,
-                           softmax_scale * LOG2E, (bf16*)out, lse);
-      } else if (forced == 8) {  // eight waves, 512 queries per workgroup (A/B)
-        dim3 grid(((seqlen + 511) / 512) * heads * batch);
-        hipLaunchKernelGGL((fwd2_bf16_kernel<2, 8>), grid, dim3(512), FWD_LDS, s, (const bf16*)qkv,
-                           key_valid, slopes, seqlen, heads, softmax_scale * LOG2E, (bf16*)out, lse);
-      } else {
-        dim3 grid(((seqlen + BQ2 - 1) / BQ2) * heads * batch);
-        hipLaunchKernelGGL((fwd2_bf16_kernel<2>), grid, dim3(256), FWD_LDS, s, (const bf16*)qkv,
-                           key_valid, slopes, seqlen, heads, softmax_scale * LOG2E, (bf16*)out, lse);
-      }
     }
   } else {
     dim3 grid((seqlen + F32_TILE - 1) / F32_TILE, heads, batch);
@@ -2588,63 +2068,58 @@ extern "C" int dna_attn_fwd(const void* qkv, const uint8_t* key_valid, const flo
   return DNA_OK;
 }
 
-template <int KB>
-static void launch_bwd3(const void* qkv, const void* out, const void* dout, const float* lse,
-                        const uint8_t* key_valid, const float* slopes, int batch, int heads, float c,
-                        float scale, void* dqkv, float* dbias_part, hipStream_t s) {
-  static const bool attr = [] {
-    const void* ks[] = {(const void*)bwd3_bf16_kernel<KB, 0>, (const void*)bwd3_bf16_kernel<KB, 1>,
-                        (const void*)bwd3_bf16_kernel<KB, 2>, (const void*)bwd3_bf16_kernel<KB, 3>};
-    for (const void* k : ks)
-      (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bwd3_lds<KB>());
-    return true;
-  }();
-  (void)attr;
-  // DNA_ATTN_BWD3_SB=1 (A/B): per-step sched_barriers in the software-pipelined phase 1
-  static const bool sb = getenv("DNA_ATTN_BWD3_SB") && atoi(getenv("DNA_ATTN_BWD3_SB")) == 1;
-  const dim3 grid(batch * heads);
-  const size_t lds = bwd3_lds<KB>();
-  auto args = [&](auto kern, float* part) {
-    hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, (const bf16*)qkv, (const bf16*)out,
-                       (const bf16*)dout, lse, key_valid, slopes, heads, c, scale, (bf16*)dqkv, part);
-  };
-  if (!dbias_part) {
-    if (sb) args(bwd3_bf16_kernel<KB, 2>, nullptr);
-    else args(bwd3_bf16_kernel<KB, 0>, nullptr);
-  } else {
-    if (sb) args(bwd3_bf16_kernel<KB, 3>, dbias_part);
-    else args(bwd3_bf16_kernel<KB, 1>, dbias_part);
-  }
-}
+// What every bf16 backward launch is given (the kernels take c = scale * log2(e) as well)
+struct BwdArgs {
+  const bf16 *qkv, *out, *dout;
+  const float* lse;
+  const uint8_t* key_valid;
+  const float* slopes;
+  int batch, seqlen, heads;
+  float scale;
+  bf16* dqkv;
+  float* delta;       // workspace of the v2 pair: written by dq2, read by dkdv2
+  float* dbias_part;  // null: no bias-gradient partial rows
+  hipStream_t stream;
+};
 
-template <int KB>
-static void launch_bwd3w8(const void* qkv, const void* out, const void* dout, const float* lse,
-                          const uint8_t* key_valid, const float* slopes, int batch, int heads,
-                          float c, float scale, void* dqkv, float* dbias_part, hipStream_t s) {
-  static const bool attr = [] {
-    const void* ks[] = {(const void*)bwd3w8_bf16_kernel<KB, false>, (const void*)bwd3w8_bf16_kernel<KB, true>};
-    for (const void* k : ks)
-      (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bwd8_lds<KB>());
-    return true;
-  }();
-  (void)attr;
-  const dim3 grid(batch * heads);
-  const size_t lds = bwd8_lds<KB>();
-  auto args = [&](auto kern, float* part) {
-    hipLaunchKernelGGL(kern, grid, dim3(512), lds, s, (const bf16*)qkv, (const bf16*)out,
-                       (const bf16*)dout, lse, key_valid, slopes, heads, c, scale, (bf16*)dqkv, part);
-  };
-  if (!dbias_part) args(bwd3w8_bf16_kernel<KB, false>, nullptr);
-  else args(bwd3w8_bf16_kernel<KB, true>, dbias_part);
-}
-
-// waves per workgroup of the fused backward at S = 256 / 512: DNA_ATTN_BWD3_NW = 4 or 8, read once.
-// Unset: 8 at S = 512 (attn_bwd 1.91 -> 1.71 ms per launch in the DNABERT-2 bench, b = 512,
-// interleaved A/B in profiles/r07/ab_attn_bwd_8wave.txt), 4 at S = 256 (not measured in a
-// training step)
-static int bwd3_nw_default(int seqlen) {
-  static const int nw = getenv("DNA_ATTN_BWD3_NW") ? atoi(getenv("DNA_ATTN_BWD3_NW")) : 0;
+// Waves per workgroup (4 or 8) of the fused backward that serves (dtype, seqlen), 0 if there is
+// none. nw = 4 or 8 asks for that many waves; nw = 0 takes DNA_ATTN_BWD3_NW, else the default.
+static int fused_bwd_waves(int dtype, int seqlen, int nw) {
+  if (dtype != DNA_BF16) return 0;
+  if (seqlen == 128) return nw == 8 ? 0 : 4;  // one 4-wave workgroup, whatever the environment
+  if (seqlen != 256 && seqlen != 512) return 0;
+  if (!nw) nw = attn_env().bwd3_nw.value;
   return nw ? nw : (seqlen == 512 ? 8 : 4);
+}
+
+// One fused-backward launch: the kernel without and with the bias-gradient partial rows, its
+// threads per workgroup and its LDS bytes (above the 64 KiB a kernel gets without asking)
+template <auto Plain, auto WithDbias, int THREADS, size_t LDS>
+static void launch_fused_bwd(const BwdArgs& a) {
+  static const bool attr = [] {
+    for (const void* k : {(const void*)Plain, (const void*)WithDbias})
+      (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS);
+    return true;
+  }();
+  (void)attr;
+  const auto kern = a.dbias_part ? WithDbias : Plain;
+  hipLaunchKernelGGL(kern, dim3(a.batch * a.heads), dim3(THREADS), LDS, a.stream, a.qkv, a.out,
+                     a.dout, a.lse, a.key_valid, a.slopes, a.heads, a.scale * LOG2E, a.scale,
+                     a.dqkv, a.dbias_part);
+}
+
+// The v2 pair with NW waves (NW * 32 queries / keys) per workgroup. The dQ kernel also produces
+// delta = rowsum(dO*O), consumed by the dK/dV kernel after it. Colsum scratch: NW*32 rows x 64 floats.
+template <int NW>
+static void launch_bwd2(const BwdArgs& a) {
+  const size_t red = a.dbias_part ? NW * 32 * 64 * sizeof(float) : 0;
+  const dim3 grid(((a.seqlen + NW * 32 - 1) / (NW * 32)) * a.heads * a.batch), block(NW * 64);
+  hipLaunchKernelGGL((dq2_bf16_kernel<NW>), grid, block, std::max(FWD_LDS, red), a.stream, a.qkv,
+                     a.out, a.dout, a.lse, a.delta, a.key_valid, a.slopes, a.seqlen, a.heads,
+                     a.scale * LOG2E, a.scale, a.dqkv, a.dbias_part);
+  hipLaunchKernelGGL((dkdv2_bf16_kernel<NW>), grid, block, std::max(DKDV2_LDS, red), a.stream,
+                     a.qkv, a.dout, a.lse, a.delta, a.key_valid, a.slopes, a.seqlen, a.heads,
+                     a.scale * LOG2E, a.scale, a.dqkv, a.dbias_part);
 }
 
 // nw: 0 = the DNA_ATTN_BWD / DNA_ATTN_BWD3_NW defaults, 4 or 8 = the fused kernel with that many waves
@@ -2656,67 +2131,35 @@ static int attn_bwd_impl(const void* qkv, const void* out, const void* dout, con
   if (st) return st;
   DNA_CHECK_ARG(out && dout && lse && dqkv && delta_ws, "dna_attn_bwd: null pointer");
   hipStream_t s = as_stream(stream);
-  const int rows = batch * seqlen;
-  const int nd = (rows * heads + 255) / 256;
-  // DNA_ATTN_BWD: 3 (default) fused one-workgroup-per-(batch, head) kernel where S is 128, 256
-  // or 512, else the v2 pair; 2 forces the v2 pair, 1 the v1 pair (benchmarks / A/B)
-  static const int bwd_env = getenv("DNA_ATTN_BWD") ? atoi(getenv("DNA_ATTN_BWD")) : 3;
-  const int bwd_ver = nw ? 3 : bwd_env;
-  const bool bwd_v1 = bwd_ver == 1;
-  if (dtype == DNA_BF16 && bwd_ver == 3 && (seqlen == 128 || seqlen == 256 || seqlen == 512)) {
-    const float c = softmax_scale * LOG2E;
-    const bool w8 = (nw ? nw : bwd3_nw_default(seqlen)) == 8 && seqlen != 128;
-    if (w8 && seqlen == 512)
-      launch_bwd3w8<2>(qkv, out, dout, lse, key_valid, slopes, batch, heads, c, softmax_scale, dqkv, dbias_part, s);
-    else if (w8)
-      launch_bwd3w8<1>(qkv, out, dout, lse, key_valid, slopes, batch, heads, c, softmax_scale, dqkv, dbias_part, s);
-    else if (seqlen == 512)
-      launch_bwd3<4>(qkv, out, dout, lse, key_valid, slopes, batch, heads, c, softmax_scale, dqkv, dbias_part, s);
-    else if (seqlen == 256)
-      launch_bwd3<2>(qkv, out, dout, lse, key_valid, slopes, batch, heads, c, softmax_scale, dqkv, dbias_part, s);
+  if (dtype == DNA_BF16) {
+    const AttnEnv& env = attn_env();
+    for (const EnvSwitch* e : {&env.bwd, &env.bwd3_nw, &env.bwd_nw})
+      if ((st = check_env(*e, "dna_attn_bwd"))) return st;
+    const BwdArgs a = {(const bf16*)qkv, (const bf16*)out, (const bf16*)dout, lse, key_valid, slopes,
+                       batch, seqlen, heads, softmax_scale, (bf16*)dqkv, delta_ws, dbias_part, s};
+    // the fused one-workgroup-per-(batch, head) kernel where there is one, else the v2 pair in
+    // 8-wave workgroups when the sequence fills them (half the K/V and Q/dO re-streaming of
+    // 4-wave ones)
+    const int fused = (nw || env.bwd.value == 3) ? fused_bwd_waves(dtype, seqlen, nw) : 0;
+    if (fused == 8 && seqlen == 512)
+      launch_fused_bwd<bwd3w8_bf16_kernel<2, false>, bwd3w8_bf16_kernel<2, true>, 512, bwd8_lds<2>()>(a);
+    else if (fused == 8)
+      launch_fused_bwd<bwd3w8_bf16_kernel<1, false>, bwd3w8_bf16_kernel<1, true>, 512, bwd8_lds<1>()>(a);
+    else if (fused && seqlen == 512)
+      launch_fused_bwd<bwd3_bf16_kernel<4, false>, bwd3_bf16_kernel<4, true>, 256, bwd3_lds<4>()>(a);
+    else if (fused && seqlen == 256)
+      launch_fused_bwd<bwd3_bf16_kernel<2, false>, bwd3_bf16_kernel<2, true>, 256, bwd3_lds<2>()>(a);
+    else if (fused)
+      launch_fused_bwd<bwd3_bf16_kernel<1, false>, bwd3_bf16_kernel<1, true>, 256, bwd3_lds<1>()>(a);
+    else if (env.bwd_nw.value == 8 && seqlen % 256 == 0)
+      launch_bwd2<8>(a);
     else
-      launch_bwd3<1>(qkv, out, dout, lse, key_valid, slopes, batch, heads, c, softmax_scale, dqkv, dbias_part, s);
-  } else if (dtype == DNA_BF16 && !bwd_v1) {
-    // dQ kernel also produces delta = rowsum(dO*O), consumed by the dK/dV kernel after it.
-    // 8-wave workgroups (256 queries / keys each) when the sequence fills them: half the
-    // K/V and Q/dO re-streaming of 4-wave ones. Colsum scratch: NW*32 rows x 64 floats.
-    static const int nw_env = getenv("DNA_ATTN_BWD_NW") ? atoi(getenv("DNA_ATTN_BWD_NW")) : 8;
-    const bool w8 = nw_env == 8 && seqlen % 256 == 0;
-    const size_t red = (w8 ? 8 : 4) * 32 * 64 * sizeof(float);
-    const size_t dq_lds = std::max(FWD_LDS, dbias_part ? red : (size_t)0);
-    const size_t kv_lds = std::max(DKDV2_LDS, dbias_part ? red : (size_t)0);
-    if (w8) {
-      hipLaunchKernelGGL((dq2_bf16_kernel<8>), dim3((seqlen / 256) * heads * batch), dim3(512),
-                         dq_lds, s, (const bf16*)qkv, (const bf16*)out, (const bf16*)dout, lse,
-                         delta_ws, key_valid, slopes, seqlen, heads, softmax_scale * LOG2E,
-                         softmax_scale, (bf16*)dqkv, dbias_part);
-      hipLaunchKernelGGL((dkdv2_bf16_kernel<8>), dim3((seqlen / 256) * heads * batch), dim3(512),
-                         kv_lds, s, (const bf16*)qkv, (const bf16*)dout, lse, delta_ws, key_valid,
-                         slopes, seqlen, heads, softmax_scale * LOG2E, softmax_scale, (bf16*)dqkv,
-                         dbias_part);
-    } else {
-      hipLaunchKernelGGL((dq2_bf16_kernel<4>), dim3(((seqlen + BQ - 1) / BQ) * heads * batch),
-                         dim3(256), dq_lds, s, (const bf16*)qkv, (const bf16*)out,
-                         (const bf16*)dout, lse, delta_ws, key_valid, slopes, seqlen, heads,
-                         softmax_scale * LOG2E, softmax_scale, (bf16*)dqkv, dbias_part);
-      hipLaunchKernelGGL((dkdv2_bf16_kernel<4>), dim3(((seqlen + BKW - 1) / BKW) * heads * batch),
-                         dim3(256), kv_lds, s, (const bf16*)qkv, (const bf16*)dout, lse, delta_ws,
-                         key_valid, slopes, seqlen, heads, softmax_scale * LOG2E, softmax_scale,
-                         (bf16*)dqkv, dbias_part);
-    }
-  } else if (dtype == DNA_BF16) {  // v1 kernels (DNA_ATTN_BWD=1, benchmarks)
-    hipLaunchKernelGGL(dq_bf16_kernel, dim3(((seqlen + BQ - 1) / BQ) * heads * batch), dim3(256),
-                       FWD_LDS, s, (const bf16*)qkv, (const bf16*)out, (const bf16*)dout, lse,
-                       delta_ws, key_valid, slopes, seqlen, heads, softmax_scale * LOG2E,
-                       softmax_scale, (bf16*)dqkv, dbias_part);
-    hipLaunchKernelGGL(dkdv_bf16_kernel, dim3(((seqlen + BKW - 1) / BKW) * heads * batch), dim3(256),
-                       DKDV_LDS, s, (const bf16*)qkv, (const bf16*)dout, lse, delta_ws, key_valid,
-                       slopes, seqlen, heads, softmax_scale * LOG2E, softmax_scale, (bf16*)dqkv,
-                       dbias_part);
+      launch_bwd2<4>(a);
   } else {
     DNA_CHECK_ARG(!dbias_part, "dna_attn_bwd_ex: fused bias-gradient partials need the bf16 path");
-    hipLaunchKernelGGL(delta_kernel<float>, dim3(nd), dim3(256), 0, s, (const float*)out,
-                       (const float*)dout, rows, heads, seqlen, delta_ws);
+    const int rows = batch * seqlen;
+    hipLaunchKernelGGL(delta_kernel<float>, dim3((rows * heads + 255) / 256), dim3(256), 0, s,
+                       (const float*)out, (const float*)dout, rows, heads, seqlen, delta_ws);
     dim3 grid((seqlen + F32_TILE - 1) / F32_TILE, heads, batch);
     hipLaunchKernelGGL(dq_f32_kernel, grid, dim3(64), 0, s, (const float*)qkv, (const float*)dout,
                        lse, delta_ws, key_valid, slopes, seqlen, heads, softmax_scale,
@@ -2744,7 +2187,7 @@ extern "C" int dna_attn_bwd_var(const void* qkv, const void* out, const void* do
                                 float softmax_scale, void* dqkv, float* delta_ws, float* dbias_part,
                                 int nw, void* stream) {
   DNA_CHECK_ARG(nw == 4 || nw == 8, "dna_attn_bwd_var: nw %d (4 or 8)", nw);
-  if (dtype != DNA_BF16 || !(seqlen == 512 || seqlen == 256 || (nw == 4 && seqlen == 128))) {
+  if (!fused_bwd_waves(dtype, seqlen, nw)) {
     set_error("dna_attn_bwd_var: no %d-wave fused backward for dtype %d, seqlen %d", nw, dtype, seqlen);
     return DNA_ERR_UNSUPPORTED;
   }

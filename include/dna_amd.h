@@ -97,10 +97,19 @@ int dna_attn_bwd_ex(const void* qkv, const void* out, const void* dout, const fl
                     int head_dim, int dtype, float softmax_scale, void* dqkv, float* delta_ws,
                     float* dbias_part, void* stream);
 /* dna_attn_bwd_ex with the fused one-workgroup-per-(batch, head) bf16 kernel chosen by its
- * waves per workgroup, nw = 4 or 8, whatever DNA_ATTN_BWD / DNA_ATTN_BWD3_NW say (tests and A/B
- * runs compare both in one process). nw = 4: seqlen 128, 256 or 512; nw = 8: seqlen 256 or 512;
- * anything else is DNA_ERR_UNSUPPORTED. dK, dV and dbias_part are bit-identical between the
- * two; dQ sums its key partials in a different (fixed) order. */
+ * waves per workgroup, nw = 4 or 8, whichever kernel DNA_ATTN_BWD / DNA_ATTN_BWD3_NW would pick
+ * (tests and A/B runs compare both in one process). nw = 4: seqlen 128, 256 or 512; nw = 8:
+ * seqlen 256 or 512; anything else is DNA_ERR_UNSUPPORTED. dK, dV and dbias_part are
+ * bit-identical between the two; dQ sums its key partials in a different (fixed) order.
+ *
+ * Environment switches of the bf16 attention, read once per process (benchmarks and A/B runs):
+ *   DNA_ATTN_FWD=2          register-staged forward where the default is the LDS-DMA ring (0)
+ *   DNA_ATTN_BWD=2          the two-kernel backward at every seqlen (default 3: fused where there
+ *                           is a fused kernel)
+ *   DNA_ATTN_BWD3_NW=4|8    waves of the fused backward at seqlen 256 / 512 (default 0: 4 / 8)
+ *   DNA_ATTN_BWD_NW=4|8     waves of the two-kernel backward where seqlen % 256 == 0 (default 8)
+ * Any other value makes dna_attn_fwd / dna_attn_bwd* return DNA_ERR_UNSUPPORTED before anything
+ * is launched: there is no quiet fall-back to the default. */
 int dna_attn_bwd_var(const void* qkv, const void* out, const void* dout, const float* lse,
                      const uint8_t* key_valid, const float* slopes, int batch, int seqlen, int heads,
                      int head_dim, int dtype, float softmax_scale, void* dqkv, float* delta_ws,

@@ -37,7 +37,10 @@ def _qkv(b, S, H, dtype, pad_rows=(), seed=0):
 @pytest.mark.parametrize("dtype,tol", [(torch.float32, 2e-5), (torch.bfloat16, 3e-2)])
 @pytest.mark.parametrize("b,S,H,pads", [(2, 128, 2, [(1, 77)]), (1, 512, 12, []),
                                         (3, 64, 1, [(0, 5), (2, 63)]), (2, 256, 4, [(0, 200)]),
-                                        (1, 2048, 2, [(0, 1500)])])  # 32 tiles through the ring
+                                        (1, 2048, 2, [(0, 1500)]),  # 32 tiles through the ring
+                                        # first length whose K/V ring and pad-bias row pass 96 KiB
+                                        # of LDS: bf16 takes the register-staged forward
+                                        (1, 12352, 1, [(0, 12000)])])
 def test_attention_forward(dtype, tol, b, S, H, pads):
     from dna_amd import functional as DF
     from dna_amd.config import alibi_slopes
@@ -52,7 +55,9 @@ def test_attention_forward(dtype, tol, b, S, H, pads):
 
 @pytest.mark.parametrize("dtype,tol", [(torch.float32, 1e-4), (torch.bfloat16, 6e-2)])
 @pytest.mark.parametrize("b,S,H,pads", [(2, 128, 2, [(1, 77)]), (1, 512, 12, [(0, 400)]),
-                                        (2, 64, 1, [])])
+                                        (2, 64, 1, []),
+                                        # smallest length on the 8-wave dq2 / dkdv2 pair (bf16)
+                                        (1, 768, 2, [(0, 700)])])
 def test_attention_backward(dtype, tol, b, S, H, pads):
     from dna_amd import functional as DF
     from dna_amd.config import alibi_slopes
@@ -74,7 +79,7 @@ def test_attention_backward(dtype, tol, b, S, H, pads):
 
 
 @pytest.mark.parametrize("b,S,H,pads", [(2, 128, 2, [(1, 77)]), (3, 512, 12, [(0, 400)]),
-                                        (1, 192, 3, [])])
+                                        (1, 192, 3, []), (1, 768, 2, [(0, 700)])])
 def test_attention_backward_fused_bias_grad(b, S, H, pads):
     """bf16 backward with the fused column sums of dqkv (bias gradient of the QKV projection):
     same dqkv as without, and the fp32 column sums match dqkv's (pre-rounding values vs rounded:

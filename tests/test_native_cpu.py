@@ -13,7 +13,7 @@ import torch
 
 from oracle import hg38_ref
 from oracle.bpe import BPERef
-from tests.conftest import BPE_JSON, GOLDEN
+from tests.conftest import BPE_JSON, GOLDEN, ROOT
 
 
 def _windows():
@@ -39,6 +39,42 @@ def test_error_reporting():
     assert "cannot open" in N.last_error()
     with pytest.raises(N.NativeError):
         N.call("dna_fasta_interval", None, b"chr1", 0, 10, 10, 0, 0, None, 0, None)
+
+
+_ATTN_ENV_CHILD = """
+import ctypes, sys
+from dna_amd import _native as N
+L = N.lib()
+buf = (ctypes.c_char * (1 << 16))()  # host memory: the call must fail before anything reads it
+p = ctypes.addressof(buf)
+if sys.argv[1] == "dna_attn_fwd":
+    st = L.dna_attn_fwd(p, None, p, 1, 64, 1, 64, N.BF16, 0.125, p, p, None)
+else:
+    st = L.dna_attn_bwd_ex(p, p, p, p, None, p, 1, 64, 1, 64, N.BF16, 0.125, p, p, None, None)
+print(st)
+print(N.last_error())
+"""
+
+
+@pytest.mark.parametrize("fn,var,value", [("dna_attn_fwd", "DNA_ATTN_FWD", "1"),
+                                          ("dna_attn_fwd", "DNA_ATTN_FWD", "8"),
+                                          ("dna_attn_fwd", "DNA_ATTN_FWD", "7"),
+                                          ("dna_attn_bwd_ex", "DNA_ATTN_BWD", "1")])
+def test_attention_env_switch_without_a_kernel_is_an_error(fn, var, value):
+    """No quiet fall-back: a DNA_ATTN_* value that selects no kernel (one of the removed variants,
+    or anything unrecognised) fails the call, before the first HIP call, with the variable named.
+    The switches are read once per process, hence the child; the GPU is hidden from it so that
+    the dummy host buffers can never reach a kernel."""
+    import subprocess
+    import sys
+    env = dict(os.environ, HIP_VISIBLE_DEVICES="-1", CUDA_VISIBLE_DEVICES="-1")
+    env[var] = value
+    r = subprocess.run([sys.executable, "-c", _ATTN_ENV_CHILD, fn], cwd=ROOT, env=env,
+                       capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr
+    status, msg = r.stdout.strip().split("\n", 1)
+    assert int(status) == 3, (status, msg)  # DNA_ERR_UNSUPPORTED
+    assert f"{var}={value}" in msg and "accepted" in msg, msg
 
 
 def test_cpp_bpe_full_encode_bit_exact():
