@@ -122,6 +122,12 @@ _SIGS = {
     "dna_cls_head_bwd_workspace": (_sz, [_i, _i, _i]),
     "dna_cls_head_bwd": (_i, [_vp, _vp, _vp, _i, _i64, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _u64,
                               _u64, _vp, _vp, _vp, _vp, _vp, _i, _vp, _sz, _vp]),
+    "dna_pool_head_fwd_workspace": (_sz, [_i, _i, _i]),
+    "dna_pool_head_fwd": (_i, [_vp, _i64, _vp, _i64, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp,
+                               _vp, _vp, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "dna_pool_head_bwd_workspace": (_sz, [_i, _i, _i]),
+    "dna_pool_head_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _i64, _vp,
+                               _i64, _i, _vp, _vp, _i, _vp, _sz, _vp]),
     "dna_sumsq_workspace": (_sz, [_sz]),
     "dna_sumsq": (_i, [_vp, _sz, _vp, _vp, _sz, _vp]),
     "dna_adamw_step": (_i, [_vp, _vp, _vp, _vp, _vp, _sz, _f, _f, _f, _f, _f, _i, _vp, _f, _f,

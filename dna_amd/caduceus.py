@@ -334,26 +334,33 @@ def weighted_cross_entropy(logits, y, loss_weights, ignore_index=-100):
     return (ce * (w / w.sum())).sum()
 
 
+def _resolve_config(who, config):
+    """DEFAULTS updated by `config` the way CaduceusConfig / CaduceusPreTrainedModel settle it: the
+    vocabulary padded to its multiple, the complement map extended over the padded ids."""
+    cfg = dict(DEFAULTS)
+    unknown = set(config) - set(DEFAULTS)
+    if unknown:
+        raise TypeError(f"{who}: unknown config keys {sorted(unknown)}")
+    cfg.update(config)
+    if cfg["rcps"] and cfg["complement_map"] is None:
+        raise ValueError("Complement map must be provided for RCPS.")   # :331
+    if cfg["vocab_size"] % cfg["pad_vocab_size_multiple"]:
+        cfg["vocab_size"] += cfg["pad_vocab_size_multiple"] - cfg["vocab_size"] % cfg["pad_vocab_size_multiple"]
+    if cfg["complement_map"] is not None:   # :336-338 -- padded ids complement to themselves
+        cm = cfg["complement_map"]
+        cm = dict(cm) if isinstance(cm, dict) else dict(enumerate(cm))
+        for i in range(len(cm), cfg["vocab_size"]):
+            cm[i] = i
+        cfg["complement_map"] = cm
+    return cfg
+
+
 class CaduceusForMaskedLM(nn.Module):
     """CaduceusForMaskedLM. forward(input_ids, labels=None, loss_weights=None) -> (loss, logits)."""
 
     def __init__(self, **config):
         super().__init__()
-        cfg = dict(DEFAULTS)
-        unknown = set(config) - set(DEFAULTS)
-        if unknown:
-            raise TypeError(f"CaduceusForMaskedLM: unknown config keys {sorted(unknown)}")
-        cfg.update(config)
-        if cfg["rcps"] and cfg["complement_map"] is None:
-            raise ValueError("Complement map must be provided for RCPS.")   # :331
-        if cfg["vocab_size"] % cfg["pad_vocab_size_multiple"]:
-            cfg["vocab_size"] += cfg["pad_vocab_size_multiple"] - cfg["vocab_size"] % cfg["pad_vocab_size_multiple"]
-        if cfg["complement_map"] is not None:   # :336-338 -- padded ids complement to themselves
-            cm = cfg["complement_map"]
-            cm = dict(cm) if isinstance(cm, dict) else dict(enumerate(cm))
-            for i in range(len(cm), cfg["vocab_size"]):
-                cm[i] = i
-            cfg["complement_map"] = cm
+        cfg = _resolve_config("CaduceusForMaskedLM", config)
         self.config = cfg
         self.caduceus = Caduceus(cfg)
         if cfg["rcps"]:
@@ -387,4 +394,89 @@ class CaduceusForMaskedLM(nn.Module):
                 ce = F.cross_entropy(logits.view(-1, logits.shape[-1]), y, ignore_index=ig,
                                      reduction="none")
                 loss = ce.sum() / (y != ig).sum()
+        return loss, logits
+
+
+POOLING = ("mean", "first", "last")
+
+
+class CaduceusForSequenceClassification(nn.Module):
+    """CaduceusForSequenceClassification (modeling_caduceus.py:476-620): the backbone, a pooling
+    over the sequence and the bias-free `score` linear, as one fused head (functional.PoolHead,
+    csrc/pool_head.hip). forward(input_ids, labels=None) -> (loss, logits).
+
+    rcps=True: the hidden state is [forward strand | reverse complement flipped over length and
+    channels] and the reference averages `score` over the first half and the flipped-back second
+    half; the head reads both halves in place, the second with its channels reversed and its
+    window mirrored along the sequence (`first` is the second half's last position, `last` its
+    first; a mean does not see the flip). conjoin_train, or conjoin_eval in eval mode: input_ids
+    is [B, L, 2] (strand, reverse complement), two backbone passes, one head call over both
+    outputs. pooling_strategy mean | first | last; max is not built."""
+
+    def __init__(self, pooling_strategy="mean", conjoin_train=False, conjoin_eval=False,
+                 num_labels=2, problem_type=None, **config):
+        super().__init__()
+        if pooling_strategy == "max":
+            raise NotImplementedError("CaduceusForSequenceClassification pooling_strategy='max' is "
+                                      f"not built ({POOLING} are)")
+        if pooling_strategy not in POOLING:
+            raise NotImplementedError(f"Pooling strategy `{pooling_strategy}` not implemented.")
+        cfg = _resolve_config("CaduceusForSequenceClassification", config)
+        self.config = cfg
+        self.pooling_strategy = pooling_strategy
+        self.conjoin_train, self.conjoin_eval = conjoin_train, conjoin_eval
+        self.num_labels = int(num_labels)
+        self.problem_type = problem_type
+        self.caduceus = Caduceus(cfg)
+        self.score = nn.Linear(cfg["d_model"], self.num_labels, bias=False)
+        ic = cfg["initializer_cfg"] or {}
+        self.apply(lambda m: _init_weights(m, cfg["n_layer"], **ic))
+        self.init_scorer()
+
+    def init_scorer(self, initializer_range=0.02):
+        ic = self.config["initializer_cfg"] or {}
+        self.score.weight.data.normal_(std=ic.get("initializer_range", initializer_range))
+
+    def _window(self, B, L, device):
+        if self.pooling_strategy == "mean":
+            return None, None
+        one = torch.ones(B, device=device, dtype=torch.int32)
+        if self.pooling_strategy == "first":
+            return None, one
+        return torch.full((B,), L - 1, device=device, dtype=torch.int32), one
+
+    def _problem(self, labels):
+        if self.problem_type is None:   # :596-602
+            if self.num_labels == 1:
+                self.problem_type = "regression"
+            elif labels.dtype in (torch.long, torch.int):
+                self.problem_type = "single_label_classification"
+            else:
+                self.problem_type = "multi_label_classification"
+        return self.problem_type
+
+    def cls_logits(self, input_ids, labels=None):
+        """-> (logits [B, num_labels] fp32, loss | None, pred | None)."""
+        kw = {}
+        if labels is not None:
+            kw = dict(labels=labels, problem_type=self._problem(labels))
+        w = self.score.weight
+        if self.config["rcps"]:
+            h = self.caduceus(input_ids)
+            start, count = self._window(h.shape[0], h.shape[1], h.device)
+            return DF.pool_head(h, w, rcps=True, mirror2=True, start=start, count=count, **kw)
+        if self.conjoin_train or (self.conjoin_eval and not self.training):
+            if input_ids.dim() != 3 or input_ids.shape[-1] != 2:
+                raise ValueError("`input_ids` must be [B, L, 2] for conjoining: the strand and its "
+                                 f"reverse complement (got {tuple(input_ids.shape)})")
+            h = self.caduceus(input_ids[..., 0])
+            h_rc = self.caduceus(input_ids[..., 1])
+            start, count = self._window(h.shape[0], h.shape[1], h.device)
+            return DF.pool_head(h, w, x2=h_rc, start=start, count=count, **kw)
+        h = self.caduceus(input_ids)
+        start, count = self._window(h.shape[0], h.shape[1], h.device)
+        return DF.pool_head(h, w, start=start, count=count, **kw)
+
+    def forward(self, input_ids, labels=None):
+        logits, loss, _ = self.cls_logits(input_ids, labels)
         return loss, logits

@@ -188,6 +188,8 @@ struct LossArgs {
 // One workgroup: first the logits (an element per thread), then, behind a workgroup barrier, the
 // loss with a thread per row (b = tid, tid + 1024, ...). Row losses are added in double, per thread
 // in row order and then over the threads by a fixed tree.
+// pool_head.hip's loss_kernel restates the three losses with the row arithmetic in double: a
+// change to the label, tie or out-of-range rules here belongs there too.
 __global__ __launch_bounds__(1024) void finish_loss_kernel(LossArgs g) {
   __shared__ double red[1024];
   const int tid = threadIdx.x, B = g.B, C = g.C;

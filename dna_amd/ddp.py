@@ -98,7 +98,9 @@ class GradBucketReducer:
         self._fired = [False] * len(self.buckets)
         self._sync = True
         self.fired_in_backward = 0
-        self._handles = [p.register_post_accumulate_grad_hook(self._hook) for p in flat.params]
+        # a frozen parameter (requires_grad False) gets no gradient and takes no hook
+        self._handles = [p.register_post_accumulate_grad_hook(self._hook) for p in flat.params
+                         if p.requires_grad]
         for p in flat.params:  # contributions written directly by fused kernels report here
             p._dna_notify = self._hook
         if force is None:

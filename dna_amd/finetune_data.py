@@ -1,12 +1,15 @@
 """Labelled-sequence data for fine-tuning: GUE-layout folders (the DNABERT-2 benchmark's
 `train.csv` / `dev.csv` / `test.csv`, each row `sequence,label`), tokenised with the C++ BPE
-tokenizer as [CLS] ... [SEP], truncated to max_length, padded per batch."""
+tokenizer as [CLS] ... [SEP], truncated to max_length, padded per batch; and Genomic Benchmarks
+folders (`<dest>/<name>/<split>/<class>/*.txt`, one sequence per file), tokenised per character
+to a fixed length for the HyenaDNA / Caduceus classifiers."""
 import csv
 import os
+import random
 
 import torch
 
-from .tokenizer import DNABertTokenizer
+from .tokenizer import CharacterTokenizer, DNABertTokenizer
 
 SPLITS = ("train", "dev", "test")
 
@@ -74,3 +77,87 @@ def collate_padded(items, pad_token_id=3, multiple=64):
     for r, (ids, _) in enumerate(items):
         out[r, : ids.numel()] = ids
     return out, torch.stack([torch.as_tensor(l) for _, l in items])
+
+
+_COMPLEMENT = str.maketrans("ACGTacgt", "TGCAtgca")
+
+
+def string_reverse_complement(seq):
+    """Reversed, A<->T and C<->G in either case; any other character stays as it is."""
+    return seq[::-1].translate(_COMPLEMENT)
+
+
+class GenomicBenchmarkFolder(torch.utils.data.Dataset):
+    """One split of a Genomic Benchmarks dataset as the reference's GenomicBenchmarkDataset reads
+    it (src/dataloaders/datasets/genomic_bench_dataset.py:122-216): the folder
+    `<dest_path>/<dataset_name>/<split>/<class>/` holds one text file per sequence; split "val"
+    reads "test" (the benchmarks have no validation split). Nothing is ever downloaded: a missing
+    folder is an error that says where the files are expected.
+
+    Classes are numbered by sorted folder name. The reference numbers them in the order
+    `Path.iterdir()` lists them, which depends on the file system and can differ between the train
+    and the test folder; sorted names give every split and every machine the same labels.
+
+    Items are (ids int64 [max_length], label int64) and, with return_mask, the attention mask
+    (bool [max_length], False on padding) as a third entry. Tokenisation as the reference calls
+    its tokenizer: truncation to max_length, padding to max_length on the tokenizer's side (left
+    by default), add_eos appends [SEP] inside max_length, rc_aug replaces a sequence by its
+    reverse complement with probability 1/2 per access (`rng`: a random.Random, for seeded
+    draws). classes: the class folders another split of the dataset has (its `.classes`); a
+    split whose folders differ is an error, since a missing class would shift the labels."""
+
+    def __init__(self, dest_path, dataset_name, split, max_length, tokenizer=None, d_output=None,
+                 use_padding=True, add_eos=False, rc_aug=False, return_mask=False, rng=None,
+                 classes=None):
+        self.split = "test" if split == "val" else split
+        self.base_path = os.path.join(str(dest_path), dataset_name, self.split)
+        if not os.path.isdir(self.base_path):
+            raise FileNotFoundError(
+                f"{self.base_path}: no such folder. Genomic Benchmarks data is not downloaded "
+                f"here; put the dataset at <dest_path>/{dataset_name}/{self.split}/<class>/*.txt")
+        self.max_length = int(max_length)
+        self.tokenizer = tokenizer or CharacterTokenizer(["A", "C", "G", "T", "N"],
+                                                         self.max_length + 2)
+        self.use_padding, self.add_eos = use_padding, add_eos
+        self.rc_aug, self.return_mask = rc_aug, return_mask
+        self.rng = rng or random.Random()
+        self.classes = sorted(d for d in os.listdir(self.base_path)
+                              if os.path.isdir(os.path.join(self.base_path, d)))
+        if not self.classes:
+            raise FileNotFoundError(f"{self.base_path}: no class folders")
+        if classes is not None and list(classes) != self.classes:
+            raise ValueError(f"{self.base_path}: class folders {self.classes} differ from the "
+                             f"expected {list(classes)}; the labels would not mean the same")
+        self.all_seqs, self.all_labels = [], []
+        for label, name in enumerate(self.classes):
+            folder = os.path.join(self.base_path, name)
+            for fn in sorted(os.listdir(folder)):
+                with open(os.path.join(folder, fn)) as f:
+                    self.all_seqs.append(f.read())
+                self.all_labels.append(label)
+        self.num_labels = len(self.classes)
+        self.d_output = self.num_labels if d_output is None else int(d_output)
+
+    def __len__(self):
+        return len(self.all_labels)
+
+    @property
+    def pad_token_id(self):
+        return self.tokenizer.pad_token_id
+
+    def __getitem__(self, idx):
+        x = self.all_seqs[idx]
+        if self.rc_aug and self.rng.random() < 0.5:
+            x = string_reverse_complement(x)
+        ids = self.tokenizer(x, add_special_tokens=bool(self.add_eos),
+                             padding="max_length" if self.use_padding else False,
+                             max_length=self.max_length, truncation=True)["input_ids"]
+        ids = torch.tensor(ids, dtype=torch.int64)
+        label = torch.tensor(self.all_labels[idx], dtype=torch.int64)
+        if self.return_mask:
+            return ids, label, ids != self.pad_token_id
+        return ids, label
+
+    def collate(self, items):
+        """[(ids, label[, mask])] of one fixed length -> stacked tensors, in the same order."""
+        return tuple(torch.stack(col) for col in zip(*items))

@@ -944,6 +944,173 @@ def cls_head(x, wp, bp, wc, bc, p=0.0, rng=None, labels=None, problem_type=None)
     return ClsHead.apply(x, wp, bp, wc, bc, float(p), seed, off, labels, problem)
 
 
+# ----------------------------------------------------------------------------------- pool head
+def _pool_rows(name, x):
+    """x [B, L, W] as the pool-head kernels read it: unit channel stride, one position stride,
+    batch stride L * position stride (a strided view such as a channel slice is read in place;
+    anything else is copied). -> (x, position stride in elements)"""
+    if x.dim() != 3:
+        raise ValueError(f"dna_amd: pool head {name} must be [B, L, D], got {tuple(x.shape)}")
+    B, L, W = x.shape
+    if B == 0 or L == 0 or W == 0:
+        raise ValueError(f"dna_amd: pool head {name} is empty: {tuple(x.shape)}")
+    s = x.stride(1) if L > 1 else (x.stride(0) if B > 1 else W)
+    if x.stride(2) != 1 or s < W or (B > 1 and L > 1 and x.stride(0) != L * s):
+        x = x.contiguous()
+        s = W
+    return x, s
+
+
+def _pool_window(name, t, B):
+    if t is None:
+        return None
+    if t.dtype != torch.int32 or t.dim() != 1 or t.numel() != B:
+        raise TypeError(f"dna_amd: pool head {name} must be int32 [{B}], got {t.dtype} "
+                        f"{tuple(t.shape)}")
+    _gpu(t)
+    return t.contiguous()
+
+
+class PoolHead(torch.autograd.Function):
+    """Windowed mean over L + linear (+ loss) on csrc/pool_head.hip, the head of the HyenaDNA
+    SequenceDecoder (pool / first / last) and of CaduceusForSequenceClassification:
+
+        pooled = mean_{l in [start, start + count)} x[:, l]       (+ the same over x2, halved)
+        logits = pooled w^T (+ bias)
+        -> (logits [B, C] fp32, loss scalar | None, pred [B] int64 | None)
+
+    x [B, L, D] fp32 or bf16; a view with unit channel stride is read in place. rcps: x is
+    [B, L, 2D] and its halves are the two inputs, the second with its channels reversed (one
+    [B, L, 2D] gradient comes back). x2: a second [B, L, D] input (flip2: channels reversed).
+    mirror2: the second input's window is [L - start - count, L - start), the same positions of
+    its sequence flip. start / count: int32 [B] on the device or None (0 / L - start). w [C, D], bias [C] | None: the
+    fp32 master parameters in both precisions. Forward 2 launches + the loss's, backward 2; with
+    FlatParams direct gradients dw / dbias are added straight into the flat buffer."""
+
+    @staticmethod
+    def forward(ctx, x, x2, w, bias, start, count, rcps, flip2, mirror2, labels, problem):
+        _gpu(x, x2, w, bias, start, count, labels)
+        ctx.set_materialize_grads(False)
+        if rcps and x2 is not None:
+            raise ValueError("dna_amd: pool head takes rcps or x2, not both")
+        x, s1 = _pool_rows("x", x)
+        B, L, W = x.shape
+        s2 = 0
+        if rcps:
+            if W % 2:
+                raise ValueError(f"dna_amd: rcps pool head needs an even width, got {W}")
+            D, flip2 = W // 2, True
+            xa, xb, s2 = x[..., :D], x[..., D:], s1
+        elif x2 is not None:
+            x2, s2 = _pool_rows("x2", x2)
+            if x2.shape != x.shape or x2.dtype != x.dtype:
+                raise ValueError(f"dna_amd: pool head x2 {x2.dtype} {tuple(x2.shape)} does not "
+                                 f"match x {x.dtype} {tuple(x.shape)}")
+            D, xa, xb = W, x, x2
+        else:
+            D, xa, xb, flip2, mirror2 = W, x, None, False, False
+        flags = int(bool(flip2)) | (int(bool(mirror2)) << 1)
+        C = w.shape[0]
+        if w.dtype != torch.float32 or not w.is_contiguous() or tuple(w.shape) != (C, D):
+            raise TypeError(f"dna_amd: pool head weight must be contiguous fp32 [C, {D}], got "
+                            f"{w.dtype} {tuple(w.shape)}")
+        if bias is not None and (bias.dtype != torch.float32 or not bias.is_contiguous()
+                                 or tuple(bias.shape) != (C,)):
+            raise TypeError(f"dna_amd: pool head bias must be contiguous fp32 [{C}], got "
+                            f"{bias.dtype} {tuple(bias.shape)}")
+        dev = x.device
+        start = _pool_window("start", start, B)
+        count = _pool_window("count", count, B)
+        pooled = torch.empty(B, D, device=dev, dtype=torch.float32)
+        logits = torch.empty(B, C, device=dev, dtype=torch.float32)
+        loss = dl = pred = None
+        if labels is not None:
+            labels = _cls_labels(labels, problem, B, C)
+            loss = torch.empty(1, device=dev, dtype=torch.float32)
+            dl = torch.empty_like(logits)
+            if problem == N.CLS_SINGLE_LABEL:
+                pred = torch.empty(B, device=dev, dtype=torch.int64)
+        nws = N.lib().dna_pool_head_fwd_workspace(B, L, D)
+        ws = torch.empty(max(nws // 4, 4), device=dev, dtype=torch.float32)
+        nin = 1 if xb is None else 2
+        with _timed("pool_head_fwd", float(nin) * B * L * D * x.element_size(), kind="byte"):
+            N.call("dna_pool_head_fwd", xa.data_ptr(), s1, _p(xb), s2, flags, _dt(x),
+                   _p(start), _p(count), w.data_ptr(), _p(bias), B, L, D, C, pooled.data_ptr(),
+                   logits.data_ptr(), _p(labels), problem, _p(loss), _p(dl), _p(pred),
+                   ws.data_ptr(), ws.numel() * 4, N.stream_ptr())
+        ctx.save_for_backward(w, pooled, dl, start, count)
+        ctx.params = (w, bias)
+        ctx.cfg = (tuple(x.shape), x.dtype, D, bool(rcps), xb is not None, flags)
+        if pred is not None:
+            ctx.mark_non_differentiable(pred)
+        return logits, (None if loss is None else loss.reshape(())), pred
+
+    @staticmethod
+    def backward(ctx, dlogits, dloss, dpred):
+        w, pooled, dl, start, count = ctx.saved_tensors
+        shape, dtype, D, rcps, two, flags = ctx.cfg
+        up = None
+        if dl is not None and dloss is not None:
+            if dlogits is None:  # the usual case: only the loss was used
+                g, up = dl, dloss.detach().to(torch.float32).reshape(1).contiguous()
+            else:
+                g = (dl * dloss + dlogits).contiguous()
+        elif dlogits is not None:
+            g = dlogits.to(torch.float32).contiguous()
+        else:
+            return (None,) * 11
+        B, L, W = shape
+        C = w.shape[0]
+        dev = w.device
+        pw, pb = ctx.params
+        direct = _param_grads_direct(ctx.params)
+        if direct:
+            dw, db = pw.grad, (None if pb is None else pb.grad)
+        else:
+            dw = torch.empty_like(w)
+            db = None if pb is None else torch.empty(C, device=dev, dtype=torch.float32)
+        # dx is contiguous whatever x's strides were (autograd takes any layout); a frozen backbone
+        # needs none, and then the broadcast pass is not launched
+        need_dx = ctx.needs_input_grad[0] or (two and not rcps and ctx.needs_input_grad[1])
+        dx = dx2 = da = dbuf = None
+        if need_dx:
+            dx = torch.empty(B, L, W, device=dev, dtype=dtype)
+            if rcps:
+                da, dbuf = dx[..., :D], dx[..., D:]
+            elif two:
+                dx2 = torch.empty(B, L, W, device=dev, dtype=dtype)
+                da, dbuf = dx, dx2
+            else:
+                da = dx
+        nws = N.lib().dna_pool_head_bwd_workspace(B, L, D)
+        ws = torch.empty(max(nws // 4, 4), device=dev, dtype=torch.float32)
+        nout = (2 if two else 1) if need_dx else 0
+        es = 2 if dtype == torch.bfloat16 else 4
+        with _timed("pool_head_bwd", float(nout) * B * L * D * es, kind="byte"):
+            N.call("dna_pool_head_bwd", g.data_ptr(), _p(up), pooled.data_ptr(), w.data_ptr(),
+                   _p(start), _p(count), B, L, D, C, _DT[dtype], _p(da), W, _p(dbuf), W,
+                   flags, dw.data_ptr(), _p(db), int(direct), ws.data_ptr(), ws.numel() * 4,
+                   N.stream_ptr())
+        if direct:
+            for q in ctx.params:
+                notify = getattr(q, "_dna_notify", None) if q is not None else None
+                if notify is not None:
+                    notify(q)
+            return (dx, dx2) + (None,) * 9
+        return dx, dx2, dw, db, None, None, None, None, None, None, None
+
+
+def pool_head(x, w, bias=None, x2=None, rcps=False, flip2=False, mirror2=False, start=None,
+              count=None, labels=None, problem_type=None):
+    """PoolHead outside autocast (the kernels take x in its own dtype and the fp32 parameters, so
+    the result is the same with and without it). problem_type: a CLS_PROBLEMS name (needed with
+    labels). -> (logits, loss | None, pred | None)."""
+    problem = CLS_PROBLEMS[problem_type] if labels is not None else N.CLS_SINGLE_LABEL
+    with torch.autocast("cuda", enabled=False):
+        return PoolHead.apply(x, x2, w, bias, start, count, bool(rcps), bool(flip2), bool(mirror2),
+                              labels, problem)
+
+
 # ----------------------------------------------------------------------------------- GEMM
 def _gemm_impl():
     """"hip" (default): forward and data-gradient GEMMs on csrc/gemm.hip; "torch": hipBLASLt

@@ -247,3 +247,55 @@ class BertLMHeadModel(nn.Module):
         ids = input_ids[0]
         logits = self.lm_head(self.backbone(ids, position_ids=position_ids))
         return CausalLMOutput(logits=(logits, mask)), None
+
+
+class DNAEmbeddingModel(nn.Module):
+    """Registry model "dna_embedding" (src/models/sequence/dna_embedding.py:18-84): the LM's
+    backbone handing back its last hidden state for a downstream decoder (decoders.py). The tied
+    `lm_head.weight` is kept, unused in the forward, so that an LM checkpoint's state dict loads
+    as it is. forward(input_ids) -> (hidden_states [B, L, d_model], None)."""
+
+    def __init__(self, d_model, n_layer, d_inner, vocab_size, pad_vocab_size_multiple=1,
+                 return_hidden_state=False, **kwargs):
+        super().__init__()
+        self.d_model = d_model
+        self.return_hidden_state = return_hidden_state
+        if vocab_size % pad_vocab_size_multiple:
+            vocab_size += pad_vocab_size_multiple - vocab_size % pad_vocab_size_multiple
+        self.backbone = LMBackbone(d_model, n_layer, d_inner, vocab_size, **kwargs)
+        self.lm_head = nn.Linear(d_model, vocab_size, bias=False)
+        self.apply(partial(_init_weights, n_layer=n_layer,
+                           **(kwargs.get("initializer_cfg") or {})))
+        self.lm_head.weight = self.backbone.embeddings.word_embeddings.weight
+
+    def forward(self, input_ids, position_ids=None, inference_params=None, state=None):
+        return self.backbone(input_ids, position_ids=position_ids), None
+
+    @property
+    def d_output(self):
+        return self.d_model
+
+
+def load_backbone(model, state_dict, freeze_backbone=False, ignore_head=True):
+    """dna_embedding.py:87-151: load a pretrained LM state dict into `model` (a
+    DNAEmbeddingModel). A "model." prefix on the checkpoint's keys is stripped; every key of the
+    fresh model must be in the checkpoint (KeyError names the first that is not); keys containing
+    "head" (with ignore_head) or "decoder" keep the fresh model's values, the rest are loaded;
+    freeze_backbone turns off requires_grad on all of the model's parameters (a decoder outside it
+    stays trainable). -> the keys that kept their fresh values."""
+    sd = {(k[len("model."):] if k.startswith("model.") else k): v for k, v in state_dict.items()}
+    own = model.state_dict()
+    kept, new = [], {}
+    for key in sorted(own):
+        if key not in sd:
+            raise KeyError(f"load_backbone: {key!r} is missing from the pretrained state dict")
+        if (ignore_head and "head" in key) or "decoder" in key:
+            kept.append(key)
+            new[key] = own[key]
+        else:
+            new[key] = sd[key]
+    model.load_state_dict(new)
+    if freeze_backbone:
+        for p in model.parameters():
+            p.requires_grad = False
+    return kept

@@ -18,6 +18,9 @@ asserts (flash_attn_triton.py:849-855) -- instead of letting a kernel read out o
     torch.ops.dna_amd.cls_loss(logits, labels, problem_type, loss, dlogits, pred)
     torch.ops.dna_amd.cls_head_bwd(dlogits, x, t, a, wp, wc, p, seed, offset, dwc, dbc, dwp, dbp,
                                    dx, accumulate)
+    torch.ops.dna_amd.pool_head_fwd(x1, x2, flip2, mirror2, start, count, w, bias, pooled, logits)
+    torch.ops.dna_amd.pool_head_bwd(dlogits, pooled, w, start, count, dx1, dx2, flip2, mirror2, dw,
+                                    dbias, accumulate)
 and the reference's FlashAttention kernel slot with its own signature (flash_attn_triton.py:
 1077-1130, called at bert_layers.py:188/192 as flash_attn_qkvpacked_func(qkv, bias)), autograd
 included:
@@ -433,7 +436,87 @@ def cls_head_bwd(dlogits: torch.Tensor, x: torch.Tensor, t: torch.Tensor, a: tor
            offset, dwc.data_ptr(), dbc.data_ptr(), dwp.data_ptr(), dbp.data_ptr(), dx.data_ptr(),
            int(accumulate), ws.data_ptr(), ws.numel() * 4, N.stream_ptr())
 
+# ------------------------------------------------------------------------------- pool head
+def _pool_x(name, x):
+    _check(x.is_cuda, f"{name} must be on the GPU (no CPU fallback), got {x.device}")
+    _check(x.dtype in _DT, f"{name} dtype {x.dtype} not in {tuple(_DT)}")
+    _check(x.dim() == 3 and x.numel() > 0, f"{name} must be a non-empty [B, L, D]")
+    B, L, D = x.shape
+    s = x.stride(1) if L > 1 else (x.stride(0) if B > 1 else D)
+    _check(x.stride(2) == 1 and s >= D and (B == 1 or L == 1 or x.stride(0) == L * s),
+           f"{name} must have unit channel stride and batch stride L * position stride")
+    return s
+
+
+def _pool_win(name, t, B):
+    if t is not None:
+        _cuda_contig(name, t, (torch.int32,))
+        _check(t.dim() == 1 and t.numel() == B, f"{name} must be int32 [{B}]")
+
+
+@torch.library.custom_op("dna_amd::pool_head_fwd", mutates_args=("pooled", "logits"))
+def pool_head_fwd(x1: torch.Tensor, x2: torch.Tensor | None, flip2: bool, mirror2: bool,
+                  start: torch.Tensor | None, count: torch.Tensor | None, w: torch.Tensor,
+                  bias: torch.Tensor | None, pooled: torch.Tensor, logits: torch.Tensor) -> None:
+    """pooled = mean over the window [start, start + count) of x1 (averaged with the same over x2,
+    its channels reversed when flip2, its window mirrored along L when mirror2), logits =
+    pooled w^T (+ bias). x1, x2 [B, L, D] fp32 or
+    bf16 views with unit channel stride, read in place."""
+    s1 = _pool_x("x1", x1)
+    B, L, D = x1.shape
+    s2 = 0
+    if x2 is not None:
+        s2 = _pool_x("x2", x2)
+        _check(x2.shape == x1.shape and x2.dtype == x1.dtype, "x2 must match x1")
+    C = w.shape[0]
+    for n, t, shape in (("w", w, (C, D)), ("bias", bias, (C,)), ("pooled", pooled, (B, D)),
+                        ("logits", logits, (B, C))):
+        if t is None:
+            continue
+        _cuda_contig(n, t, (torch.float32,))
+        _check(tuple(t.shape) == shape, f"{n} must be {shape}, got {tuple(t.shape)}")
+    _pool_win("start", start, B)
+    _pool_win("count", count, B)
+    nws = N.lib().dna_pool_head_fwd_workspace(B, L, D)
+    ws = torch.empty(max(nws // 4, 4), device=x1.device, dtype=torch.float32)
+    N.call("dna_pool_head_fwd", x1.data_ptr(), s1, _p(x2), s2, int(flip2) | (int(mirror2) << 1),
+           _DT[x1.dtype],
+           _p(start), _p(count), w.data_ptr(), _p(bias), B, L, D, C, pooled.data_ptr(),
+           logits.data_ptr(), None, 0, None, None, None, ws.data_ptr(), ws.numel() * 4,
+           N.stream_ptr())
+
+
+@torch.library.custom_op("dna_amd::pool_head_bwd", mutates_args=("dx1", "dx2", "dw", "dbias"))
+def pool_head_bwd(dlogits: torch.Tensor, pooled: torch.Tensor, w: torch.Tensor,
+                  start: torch.Tensor | None, count: torch.Tensor | None, dx1: torch.Tensor,
+                  dx2: torch.Tensor | None, flip2: bool, mirror2: bool, dw: torch.Tensor,
+                  dbias: torch.Tensor | None, accumulate: bool) -> None:
+    """Backward of pool_head_fwd from dlogits: dw, dbias (accumulate: added into the buffers) and
+    dx1 / dx2 [B, L, D] (views with unit channel stride), every element written."""
+    s1 = _pool_x("dx1", dx1)
+    B, L, D = dx1.shape
+    s2 = 0
+    if dx2 is not None:
+        s2 = _pool_x("dx2", dx2)
+        _check(dx2.shape == dx1.shape and dx2.dtype == dx1.dtype, "dx2 must match dx1")
+    C = w.shape[0]
+    for n, t, shape in (("dlogits", dlogits, (B, C)), ("pooled", pooled, (B, D)), ("w", w, (C, D)),
+                        ("dw", dw, (C, D)), ("dbias", dbias, (C,))):
+        if t is None:
+            continue
+        _cuda_contig(n, t, (torch.float32,))
+        _check(tuple(t.shape) == shape, f"{n} must be {shape}, got {tuple(t.shape)}")
+    _pool_win("start", start, B)
+    _pool_win("count", count, B)
+    nws = N.lib().dna_pool_head_bwd_workspace(B, L, D)
+    ws = torch.empty(max(nws // 4, 4), device=dx1.device, dtype=torch.float32)
+    N.call("dna_pool_head_bwd", dlogits.data_ptr(), None, pooled.data_ptr(), w.data_ptr(),
+           _p(start), _p(count), B, L, D, C, _DT[dx1.dtype], dx1.data_ptr(), s1, _p(dx2), s2,
+           int(flip2) | (int(mirror2) << 1), dw.data_ptr(), _p(dbias), int(accumulate), ws.data_ptr(), ws.numel() * 4,
+           N.stream_ptr())
+
 
 OPS = ("attn_fwd", "attn_bwd", "alibi_attn_qkvpacked", "flash_attn_qkvpacked", "linear_fwd",
        "transpose_bf16", "geglu_linear_fwd", "geglu_linear_dgrad",
-       "geglu_fwd", "geglu_bwd", "xent_fwd", "cls_head_fwd", "cls_loss", "cls_head_bwd")
+       "geglu_fwd", "geglu_bwd", "xent_fwd", "cls_head_fwd", "cls_loss", "cls_head_bwd", "pool_head_fwd",
+       "pool_head_bwd")

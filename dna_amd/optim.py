@@ -22,6 +22,11 @@ class FusedAdamW:
     def __init__(self, flat, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0,
                  max_grad_norm=1.0):
         self.flat = flat
+        # elements of the flat buffers the step covers: all of them, or the leading part when the
+        # parameters behind it are frozen (trainer.SeqClsTrainer). What it leaves out gets no
+        # update, no weight decay and no share in the clip norm, like torch's AdamW and
+        # clip_grad_norm_ treat parameters without a gradient
+        self.numel = flat.numel
         dev = flat.flat.device
         self.exp_avg = torch.zeros_like(flat.flat)
         self.exp_avg_sq = torch.zeros_like(flat.flat)
@@ -36,7 +41,7 @@ class FusedAdamW:
 
     def grad_norm_sq(self):
         """Launch the global sum of squares of the gradient (device scalar, no sync)."""
-        N.call("dna_sumsq", self.flat.grad.data_ptr(), self.flat.numel, self._sumsq.data_ptr(),
+        N.call("dna_sumsq", self.flat.grad.data_ptr(), self.numel, self._sumsq.data_ptr(),
                self._ws.data_ptr(), self._nws, N.stream_ptr())
         return self._sumsq
 
@@ -49,7 +54,7 @@ class FusedAdamW:
         shadow = self.flat.shadow
         N.call("dna_adamw_step", self.flat.flat.data_ptr(), self.flat.grad.data_ptr(),
                self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(),
-               None if shadow is None else shadow.data_ptr(), self.flat.numel, g["lr"],
+               None if shadow is None else shadow.data_ptr(), self.numel, g["lr"],
                g["betas"][0], g["betas"][1], g["eps"], g["weight_decay"], self.step_count,
                self._sumsq.data_ptr() if clip else None,
                float(self.max_grad_norm or 0.0), float(grad_scale), N.stream_ptr())

@@ -247,3 +247,85 @@ class ClsTrainer:
             return self.model.cls_logits(input_ids, labels)
         finally:
             self.model.train(was)
+
+
+class SeqClsTrainer(ModuleTrainer):
+    """Fine-tuning step engine for the pooling-head classifiers (decoders.SequenceClassifier over
+    DNAEmbeddingModel, CaduceusForSequenceClassification; any model with
+    `cls_logits(input_ids, labels) -> (logits, loss, pred)`): ModuleTrainer's step -- flat fp32
+    parameters with the bf16 shadow under bf16 autocast, the head's dW / dbias added straight
+    into the flat gradient, clip + AdamW in one launch -- plus ClsTrainer's interface: LR
+    schedule, last_logits / last_pred, evaluate, RNG state for checkpoints. These models draw
+    their dropout from torch's generators, so that is the state kept. Single GPU."""
+
+    def __init__(self, model, device, lr=6e-4, weight_decay=0.1, betas=(0.9, 0.999), eps=1e-8,
+                 max_grad_norm=1.0, scheduler=None, seed=None, autocast=torch.bfloat16):
+        if dist.is_initialized() and dist.get_world_size() > 1:
+            raise NotImplementedError("SeqClsTrainer: single-GPU fine-tuning only")
+        if seed is not None:
+            torch.manual_seed(int(seed) + 0x5EED)
+        super().__init__(model, device, self._loss, lr=lr, weight_decay=weight_decay, betas=betas,
+                         eps=eps, max_grad_norm=max_grad_norm, autocast=autocast)
+        self.sched = LinearLRSchedulerWarmup(self.opt, **scheduler) if scheduler else None
+        self.opt.numel = self._trainable_extent()
+        self.last_logits = None
+        self.last_pred = None
+
+    def _trainable_extent(self):
+        """How far into the flat buffers the optimizer steps. Frozen parameters (requires_grad
+        False: hyena_lm.load_backbone(freeze_backbone=True)) must get no update and no weight
+        decay. FlatParams lays parameters out in reverse registration order, so a frozen model
+        under a trainable decoder is the tail of the buffer and the step simply stops before it;
+        any other pattern of frozen parameters is refused."""
+        flat = self.flat
+        end = 0
+        for p, (o, n, _) in zip(flat.params, flat.slices):
+            if p.requires_grad:
+                end = max(end, o + n)
+        if end == 0:
+            raise ValueError("SeqClsTrainer: no parameter requires a gradient")
+        inside = [n for p, (o, n, _) in zip(flat.params, flat.slices)
+                  if not p.requires_grad and o < end]
+        if inside:
+            raise NotImplementedError(
+                f"SeqClsTrainer: {len(inside)} frozen parameters are registered after trainable "
+                "ones; only a frozen leading sub-module (the backbone under its head) is built")
+        from .flat import ALIGN
+        return min((end + ALIGN - 1) // ALIGN * ALIGN, flat.numel)  # slices start ALIGN-aligned
+
+    def _loss(self, model, batch):
+        logits, loss, pred = model.cls_logits(*batch)
+        self.last_logits, self.last_pred = logits.detach(), pred
+        return loss
+
+    def rng_state(self):
+        st = {"cpu": torch.get_rng_state()}
+        if self.device.type == "cuda":
+            st["cuda"] = torch.cuda.get_rng_state(self.device)
+        return st
+
+    def load_rng_state(self, st):
+        torch.set_rng_state(st["cpu"])
+        if "cuda" in st and self.device.type == "cuda":
+            torch.cuda.set_rng_state(st["cuda"], self.device)
+
+    def step(self, input_ids, labels) -> torch.Tensor:
+        """One optimizer step on one batch (ids and labels on the device); no host sync."""
+        loss = super().step((input_ids, labels))
+        if self.sched is not None:
+            self.sched.step()
+        return loss
+
+    @torch.no_grad()
+    def evaluate(self, input_ids, labels=None):
+        """Eval-mode forward -> (logits, loss | None, pred | None); restores the training mode."""
+        was = self.model.training
+        self.model.eval()
+        try:
+            self._versions = _sync_shadow(self.flat, self._versions)
+            if self.autocast is not None:
+                with torch.autocast(self.device.type, dtype=self.autocast):
+                    return self.model.cls_logits(input_ids, labels)
+            return self.model.cls_logits(input_ids, labels)
+        finally:
+            self.model.train(was)

@@ -4,6 +4,8 @@
     python finetune.py dataset.data_dir=/data/GUE/prom/prom_300_all \\
         train.pretrained_model_path=checkpoints/last.ckpt trainer.max_epochs=3
     python finetune.py --dry-run                       # compose + build, no GPU
+    python finetune.py experiment=hyena/genomic_benchmark_hyena dataset.dest_path=/data/gb
+    python finetune.py experiment=caduceus/genomic_benchmark_caduceus dataset.dest_path=/data/gb
 
 `key=value` overrides are composed by dna_amd.compose over configs/ with the experiment
 dnabert2/dnabert2_gue_finetune (another one: experiment=...). The run trains with ClsTrainer
@@ -13,6 +15,15 @@ line per event, and writes the best (train.monitor / train.mode, default val/mcc
 checkpoints in train.py's Lightning layout. train.pretrained_model_path takes an MLM checkpoint
 written by train.py (the MLM head is dropped, pooler and classifier start from their
 initialisation) or a fine-tuning checkpoint.
+
+model._name_ picks the path: dnabert2_cls as above; dna_embedding (HyenaDNA backbone +
+SequenceDecoder) and caduceus_cls (CaduceusForSequenceClassification) read a Genomic Benchmarks
+folder (dataset.dest_path / dataset.dataset_name, character tokens at a fixed length), train with
+SeqClsTrainer on the fused pooling head, and share the epoch loop, metrics, events and
+checkpoints. The benchmarks have no validation split: val and test are both the test folder.
+train.pretrained_model_path there takes an LM / masked-LM checkpoint of train.py (backbone
+loaded, head fresh; dna_embedding honours train.pretrained_model_state_hook.freeze_backbone: the
+backbone then gets no update and no weight decay) or one of this script's checkpoints.
 """
 import argparse
 import json
@@ -63,14 +74,127 @@ def evaluate(trainer, ds, batch_size, device, num_labels):
     return out
 
 
+POOL_MODELS = ("dna_embedding", "caduceus_cls")
+
+
+def _char_tokenizer(max_length, padding_side="left"):
+    from dna_amd.tokenizer import CharacterTokenizer
+    return CharacterTokenizer(["A", "C", "G", "T", "N"], int(max_length) + 2,
+                              padding_side=padding_side)
+
+
+def _pool_model(cfg, num_labels, tokenizer):
+    """The model of a pooling-head experiment from cfg.model (+ cfg.decoder for dna_embedding)."""
+    mc = {k: v for k, v in cfg.model.to_container().items() if k != "_name_"}
+    if cfg.model._name_ == "dna_embedding":
+        from dna_amd.decoders import SequenceClassifier
+        from dna_amd.hyena_lm import DNAEmbeddingModel
+        dec = cfg.get("decoder")
+        dec = dec.to_container() if dec is not None else {}
+        if dec.get("_name_", "sequence") != "sequence":
+            raise NotImplementedError(f"decoder {dec.get('_name_')!r} (sequence only)")
+        return SequenceClassifier(DNAEmbeddingModel(**mc), num_labels, mode=dec.get("mode", "pool"),
+                                  use_lengths=dec.get("use_lengths", False))
+    from dna_amd.caduceus import CaduceusForSequenceClassification
+    head = {k: mc.pop(k) for k in ("pooling_strategy", "conjoin_train", "conjoin_eval") if k in mc}
+    config = mc.pop("config")
+    if mc:
+        raise TypeError(f"caduceus_cls: unknown model keys {sorted(mc)}")
+    if config.get("rcps") and config.get("complement_map") is None:
+        config["complement_map"] = tokenizer.complement_map()
+    return CaduceusForSequenceClassification(num_labels=num_labels, **head, **config)
+
+
+def load_pretrained(model, state_dict, freeze_backbone=False):
+    """train.pretrained_model_path for the pooling-head models -> what was loaded, for the log.
+    A "model." prefix (train.py's and finetune.py's checkpoint layout) is stripped first. A
+    dna_embedding classifier takes an LM checkpoint through hyena_lm.load_backbone (backbone
+    loaded, heads fresh, freeze_backbone honoured) or one of finetune.py's own checkpoints (keys
+    model.* and decoder.0.*: everything loaded, strictly). A Caduceus classifier loads whatever
+    keys match: the masked-LM backbone, or a fine-tuning checkpoint with its score."""
+    from dna_amd.decoders import SequenceClassifier
+    sd = {(k[len("model."):] if k.startswith("model.") else k): v for k, v in state_dict.items()}
+    if isinstance(model, SequenceClassifier):
+        if any(k.startswith("decoder.0.") for k in sd):
+            model.load_state_dict(sd)
+            return {"loaded": "classifier"}
+        from dna_amd.hyena_lm import load_backbone
+        return {"kept_fresh": load_backbone(model.model, sd, freeze_backbone=freeze_backbone)}
+    if freeze_backbone:
+        raise NotImplementedError("freeze_backbone is built for dna_embedding only")
+    missing, unexpected = model.load_state_dict(sd, strict=False)
+    return {"missing": list(missing), "unexpected": len(unexpected)}
+
+
+def finetune_pool(cfg, dry_run=False, out=sys.stdout):
+    """The dna_embedding / caduceus_cls path: Genomic Benchmarks folder, SeqClsTrainer."""
+    import train as T
+    from dna_amd.finetune_data import GenomicBenchmarkFolder
+
+    if T.n_devices(cfg.trainer) != 1:
+        raise NotImplementedError("finetune.py: single-GPU fine-tuning only (trainer.devices=1)")
+    seed = cfg.train.get("seed")
+    if seed is not None:
+        torch.manual_seed(int(seed))
+    precision = T._precision(cfg.trainer.get("precision", "bf16"))
+    sched = _scheduler(cfg)
+    opt = cfg.optimizer.to_container()
+    ds = cfg.dataset
+    max_length = int(ds.get("max_length", 200))
+    tok = _char_tokenizer(max_length, ds.get("padding_side", "left"))
+    if dry_run:
+        model = _pool_model(cfg, int(ds.get("d_output") or 2), tok)
+        print(json.dumps({"dry_run": True, "model": cfg.model._name_,
+                          "model_params": sum(p.numel() for p in model.parameters()),
+                          "num_labels": model.num_labels, "dest_path": ds.get("dest_path"),
+                          "dataset_name": ds.get("dataset_name"),
+                          "monitor": cfg.train.monitor, "mode": cfg.train.mode,
+                          "scheduler": sched, "optimizer": opt}), file=out)
+        return None
+    if not ds.get("dest_path"):
+        raise ValueError("dataset.dest_path=<folder holding <dataset_name>/train and /test> is "
+                         "required")
+    kw = dict(max_length=max_length, tokenizer=tok, use_padding=ds.get("use_padding", True),
+              add_eos=ds.get("add_eos", False))
+    train_ds = GenomicBenchmarkFolder(ds.dest_path, ds.dataset_name, "train",
+                                      rc_aug=ds.get("rc_aug", False), **kw)
+    test_ds = GenomicBenchmarkFolder(ds.dest_path, ds.dataset_name, "val",
+                                     classes=train_ds.classes, **kw)
+    splits = {"train": train_ds, "dev": test_ds, "test": test_ds}
+    num_labels = int(ds.get("d_output") or train_ds.num_labels)
+    model = _pool_model(cfg, num_labels, tok)
+    pre = cfg.train.get("pretrained_model_path")
+    if pre:
+        ck = torch.load(pre, map_location="cpu", weights_only=True)
+        hook = (cfg.train.get("pretrained_model_state_hook") or {})
+        info = load_pretrained(model, ck.get("state_dict", ck),
+                               freeze_backbone=bool(hook.get("freeze_backbone", False)))
+        print(json.dumps(dict({"event": "load_backbone", "path": pre}, **info)), file=out,
+              flush=True)
+    device = torch.device("cuda", 0)
+    torch.cuda.set_device(device)
+    from dna_amd.trainer import SeqClsTrainer
+    trainer = SeqClsTrainer(model, device, lr=float(opt.get("lr", 6e-4)),
+                            weight_decay=float(opt.get("weight_decay", 0.1)),
+                            betas=tuple(opt.get("betas", (0.9, 0.999))),
+                            eps=float(opt.get("eps", 1e-8)),
+                            max_grad_norm=cfg.trainer.get("gradient_clip_val", 1.0),
+                            scheduler=sched, seed=seed,
+                            autocast=torch.bfloat16 if precision == "bf16" else None)
+    return _fit(cfg, trainer, model, splits, device, out)
+
+
 def finetune(cfg, dry_run=False, out=sys.stdout):
     import train as T
     from dna_amd.bert_layers import BertForSequenceClassification
     from dna_amd.finetune_data import SequenceClassificationCSV
     from dna_amd.trainer import ClsTrainer, load_backbone
 
+    if cfg.model._name_ in POOL_MODELS:
+        return finetune_pool(cfg, dry_run=dry_run, out=out)
     if cfg.model._name_ != "dnabert2_cls":
-        raise ValueError(f"model._name_={cfg.model._name_!r}: finetune.py runs dnabert2_cls")
+        raise ValueError(f"model._name_={cfg.model._name_!r}: finetune.py runs dnabert2_cls, "
+                         + ", ".join(POOL_MODELS))
     if T.n_devices(cfg.trainer) != 1:
         raise NotImplementedError("finetune.py: single-GPU fine-tuning only (trainer.devices=1)")
     seed = cfg.train.get("seed")
@@ -114,6 +238,14 @@ def finetune(cfg, dry_run=False, out=sys.stdout):
                          betas=tuple(opt.get("betas", (0.9, 0.999))), eps=float(opt.get("eps", 1e-8)),
                          max_grad_norm=cfg.trainer.get("gradient_clip_val", 1.0), scheduler=sched,
                          seed=seed)
+    return _fit(cfg, trainer, model, splits, device, out)
+
+
+def _fit(cfg, trainer, model, splits, device, out):
+    """The epoch loop shared by every model: train, evaluate dev and test after each epoch, JSON
+    events, best and last checkpoints. -> the last epoch's metrics."""
+    import train as T
+    train_ds = splits["train"]
     ck = (cfg.get("callbacks", {}) or {}).get("model_checkpoint")
     ck = ck.to_container() if ck is not None else {}
     dirpath = ck.get("dirpath", "checkpoints/")
@@ -124,7 +256,7 @@ def finetune(cfg, dry_run=False, out=sys.stdout):
     ebs = int(cfg.dataset.get("eval_batch_size", bs))
     log_every = int(cfg.trainer.get("log_every_n_steps", 10))
     max_steps = cfg.train.get("max_steps")
-    gen = torch.Generator().manual_seed(int(seed or 0))
+    gen = torch.Generator().manual_seed(int(cfg.train.get("seed") or 0))
     print(json.dumps({"event": "start", "train": len(train_ds), "dev": len(splits["dev"]),
                       "test": len(splits["test"]), "num_labels": model.num_labels,
                       "batch_size": bs}), file=out, flush=True)

@@ -562,6 +562,49 @@ int dna_cls_head_bwd(const float* dlogits, const float* upstream, const void* x,
                      float* dx, int accumulate, void* workspace, size_t workspace_bytes,
                      void* stream);
 
+/* ------------------------------------------------------------------ pooling classification head
+ * Windowed mean over L + linear + loss of the HyenaDNA / Caduceus downstream models (reference
+ * src/tasks/decoders.py SequenceDecoder pool / first / last; caduceus modeling_caduceus.py:476-620
+ * pooling + score), csrc/pool_head.hip. For sequence b, window [start_b, start_b + count_b):
+ *   m1_b = (1 / count_b) sum_{l in window} x1[b, l, :]     m2_b the same over x2, its channels
+ *   reversed when flip2 has DNA_POOL_FLIP_CHANNELS; with DNA_POOL_MIRROR_WINDOW x2's window is
+ *   [L - start_b - count_b, L - start_b), the same positions of the sequence-flipped x2 (the
+ *   reverse-complement half of an RCPS activation is flipped along both; a whole-row mean does
+ *   not see the sequence flip)     pooled = m1, or (m1 + m2) / 2 when x2 != NULL
+ *   logits = pooled W^T (+ bias when bias != NULL)
+ * x1, x2: [B, L, D] DNA_F32 or DNA_BF16 (one dtype for both), unit channel stride, position l of
+ * sequence b at x + (b * L + l) * stride elements; the halves of an RCPS activation [B, L, 2D] in
+ * place are x2 = x1 + D with both strides 2D. start, count: int32 [B] on the device, either may be
+ * NULL (0 and L - start); both are clamped to the row on the device; count_b = 0 gives
+ * pooled_b = 0 and dx_b = 0. W [C, D], bias [C] fp32; pooled [B, D], logits [B, C] fp32 (both
+ * written). Any D >= 1 (16-byte accesses when D, the strides and the pointers are multiples of 16
+ * bytes, else element accesses in the same kernels), 1 <= C <= 64, 1 <= B <= 65,535, 64-bit
+ * indexing of x and dx. fp32 accumulation in a fixed order, no atomics: bit-identical from run
+ * to run.
+ * dna_pool_head_fwd: two launches (partial sums over chunks of L into the workspace; chunks ->
+ * pooled -> logits), plus one for the loss when labels != NULL (labels, problem_type, loss,
+ * dlogits, pred as dna_cls_loss; ignored otherwise).
+ * dna_pool_head_bwd: from dlogits (times upstream[0], a device scalar, when upstream != NULL):
+ * dW [C, D], dbias [C] (may be NULL) -- accumulate != 0: added into the buffers -- and
+ * dx1[b, l, :] = dlogits_b W / count_b inside the window (halved when dx2 != NULL), 0 outside, in
+ * x_dtype with dx1_stride; dx2 the same under the forward's flip2 flags. Every element of dx1 /
+ * dx2 is written once. Two launches. dx1 == NULL (then dx2 == NULL too): only dW and dbias, one
+ * launch -- the hidden state needs no gradient under a frozen backbone. */
+enum dna_pool_flip { DNA_POOL_FLIP_CHANNELS = 1, DNA_POOL_MIRROR_WINDOW = 2 };
+size_t dna_pool_head_fwd_workspace(int batch, int len, int width);
+int dna_pool_head_fwd(const void* x1, int64_t x1_stride, const void* x2, int64_t x2_stride,
+                      int flip2, int x_dtype, const int32_t* start, const int32_t* count,
+                      const float* W, const float* bias, int batch, int len, int width,
+                      int labels_n, float* pooled, float* logits, const void* labels,
+                      int problem_type, float* loss, float* dlogits, int64_t* pred, void* workspace,
+                      size_t workspace_bytes, void* stream);
+size_t dna_pool_head_bwd_workspace(int batch, int len, int width);
+int dna_pool_head_bwd(const float* dlogits, const float* upstream, const float* pooled,
+                      const float* W, const int32_t* start, const int32_t* count, int batch, int len,
+                      int width, int labels_n, int x_dtype, void* dx1, int64_t dx1_stride, void* dx2,
+                      int64_t dx2_stride, int flip2, float* dW, float* dbias, int accumulate,
+                      void* workspace, size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------ optimizer (flat buffers)
  * Lightning gradient_clip_val=1.0 (torch.nn.utils.clip_grad_norm_) + torch AdamW
  * (train.py:462-542, registry.optimizer["adamw"]) over ONE flat fp32 parameter buffer.
