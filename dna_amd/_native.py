@@ -24,6 +24,7 @@ _i64 = ctypes.c_int64
 
 _SIGS = {
     "dna_abi_version": (_i, []),
+    "dna_abi_revision": (_i, []),
     "dna_last_error": (ctypes.c_char_p, []),
     "dna_attn_fwd": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp]),
     "dna_attn_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp]),
@@ -128,6 +129,12 @@ _SIGS = {
     "dna_pool_head_bwd_workspace": (_sz, [_i, _i, _i]),
     "dna_pool_head_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _i64, _vp,
                                _i64, _i, _vp, _vp, _i, _vp, _sz, _vp]),
+    "dna_lm_head_fwd_workspace": (_sz, [_i]),
+    "dna_lm_head_fwd": (_i, [_vp, _i64, _i, _vp, _i, _vp, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp,
+                             _sz, _vp]),
+    "dna_lm_head_bwd_workspace": (_sz, [_i, _i, _i]),
+    "dna_lm_head_bwd": (_i, [_vp, _vp, _i64, _i, _vp, _i, _vp, _vp, _vp, _f, _i, _i, _i, _vp, _i64,
+                             _vp, _i, _vp, _sz, _vp]),
     "dna_sumsq_workspace": (_sz, [_sz]),
     "dna_sumsq": (_i, [_vp, _sz, _vp, _vp, _sz, _vp]),
     "dna_adamw_step": (_i, [_vp, _vp, _vp, _vp, _vp, _sz, _f, _f, _f, _f, _f, _i, _vp, _f, _f,

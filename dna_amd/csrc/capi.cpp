@@ -16,4 +16,5 @@ void set_error(const char* fmt, ...) {
 }  // namespace dna
 
 extern "C" int dna_abi_version(void) { return DNA_AMD_ABI_VERSION; }
+extern "C" int dna_abi_revision(void) { return DNA_AMD_ABI_REVISION; }
 extern "C" const char* dna_last_error(void) { return dna::g_err; }

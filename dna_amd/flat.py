@@ -10,6 +10,11 @@ to 64 elements; backward produces gradients roughly front-to-back through this b
 all-reduce buckets (dna_amd/ddp.py) become ready in order. The tied embedding/decoder weight is
 one parameter and therefore one slice (it sits at the end: its last contribution comes from the
 embedding backward, the final op of the backward pass).
+
+Opt-in (`group_of`): parameters with optimizer overrides (`p._optim`, the Hyena filter) are laid
+out group by group -- group 0 first, each group in reverse registration order -- so that every
+optimizer group is one contiguous extent (`group_extents`) and one AdamW launch. Without it the
+layout is exactly the one above.
 """
 import torch
 
@@ -32,8 +37,13 @@ def raw_writes():
 
 
 class FlatParams:
-    def __init__(self, module: torch.nn.Module, device=None, shadow_dtype=torch.bfloat16):
+    def __init__(self, module: torch.nn.Module, device=None, shadow_dtype=torch.bfloat16,
+                 group_of=None):
+        """group_of: None, or a function parameter -> optimizer group index (optim.param_groups_of);
+        the layout then keeps each group's parameters together, groups in index order."""
         params = list(module.parameters())[::-1]
+        if group_of is not None:
+            params = sorted(params, key=group_of)  # stable: reverse registration order per group
         device = torch.device(device) if device is not None else params[0].device
         self.params = params
         self.slices = []
@@ -44,6 +54,15 @@ class FlatParams:
             off += (n + ALIGN - 1) // ALIGN * ALIGN
         self.numel = off
         self.n_params = sum(p.numel() for p in params)
+        # [start, end) of each optimizer group in the flat buffers (ALIGN-aligned at both ends)
+        self.group_extents = None
+        if group_of is not None:
+            starts = {}
+            for p, (o, _, _) in zip(params, self.slices):
+                starts.setdefault(group_of(p), o)
+            order = sorted(starts)
+            self.group_extents = {g: (starts[g], starts[order[i + 1]] if i + 1 < len(order) else off)
+                                  for i, g in enumerate(order)}
         self.flat = torch.zeros(off, dtype=torch.float32, device=device)
         self.grad = torch.zeros(off, dtype=torch.float32, device=device)
         self._index = {}

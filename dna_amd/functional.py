@@ -781,6 +781,105 @@ class MaskedCrossEntropy(torch.autograd.Function):
         return dl, None, None
 
 
+LM_HEAD_MAX_VOCAB = 64  # csrc/lm_head.hip: a lane per vocabulary entry
+
+
+class MaskedLMHead(torch.autograd.Function):
+    """Tied LM head + masked cross entropy on csrc/lm_head.hip, for vocabularies of at most 64
+    entries (the HyenaDNA character tokenizer), without a logits tensor:
+
+        logits = h w^T (fp32);  loss = sum_{r: labels[r] >= 0} CE(logits[r], labels[r]) / count
+        -> (loss scalar fp32, count scalar int64: the kept rows, on the device)
+
+    h [T, D] fp32 or bf16; a view with unit column stride and a row stride >= D is read in place;
+    rows with a negative label are never read. w [V, D]: the fp32 master parameter; under a
+    bf16 h its bf16 shadow (`_dna_lp`, kept by the trainer) is what the kernels read. labels [T]
+    int64 (a label >= V is treated as ignored by the kernel and never indexes w; callers
+    validate labels where they are built, on the host). denom > 0 replaces count as the divisor.
+    count == 0 gives loss 0 and zero gradients (the reference's mean over an empty selection is
+    NaN). The upstream gradient stays on the device. dh comes back in h's dtype, every element
+    written by the kernel; dw is added straight into the flat gradient with FlatParams direct
+    gradients (the tied embedding adds its own share there too), else returned."""
+
+    @staticmethod
+    def forward(ctx, h, w, labels, denom):
+        _gpu(h, w, labels)
+        ctx.set_materialize_grads(False)
+        if h.dim() != 2 or h.numel() == 0:
+            raise ValueError(f"dna_amd: lm head input must be a non-empty [T, D], got {tuple(h.shape)}")
+        T, D = h.shape
+        if h.stride(1) != 1 or (T > 1 and h.stride(0) < D):
+            h = h.contiguous()
+        hs = h.stride(0) if T > 1 else D
+        V = w.shape[0]
+        if w.dtype != torch.float32 or not w.is_contiguous() or tuple(w.shape) != (V, D):
+            raise TypeError(f"dna_amd: lm head weight must be contiguous fp32 [V, {D}], got "
+                            f"{w.dtype} {tuple(w.shape)}")
+        if not 1 <= V <= LM_HEAD_MAX_VOCAB:
+            raise ValueError(f"dna_amd: lm head takes 1 <= V <= {LM_HEAD_MAX_VOCAB}, got {V}")
+        if labels.dtype != torch.int64 or labels.numel() != T:
+            raise TypeError(f"dna_amd: lm head labels must be int64 [{T}], got {labels.dtype} "
+                            f"{tuple(labels.shape)}")
+        labels = labels.reshape(-1).contiguous()
+        lp = getattr(w, "_dna_lp", None)
+        wk = lp if (h.dtype == torch.bfloat16 and lp is not None) else w
+        dev = h.device
+        need_bwd = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
+        out = torch.empty(2, device=dev, dtype=torch.float32)  # loss_sum, loss
+        count = torch.empty((), device=dev, dtype=torch.int64)
+        coef = torch.empty(T, V, device=dev, dtype=torch.float32) if need_bwd else None
+        nws = N.lib().dna_lm_head_fwd_workspace(T)
+        ws = torch.empty(max(nws // 8, 2), device=dev, dtype=torch.float64)
+        dn = 0.0 if denom is None else float(denom)
+        with _timed("lm_head_fwd", float(T) * D * h.element_size(), kind="byte"):
+            N.call("dna_lm_head_fwd", h.data_ptr(), hs, _dt(h), wk.data_ptr(), _dt(wk),
+                   labels.data_ptr(), T, D, V, dn, out.data_ptr(), count.data_ptr(),
+                   out[1:].data_ptr(), _p(coef), ws.data_ptr(), ws.numel() * 8, N.stream_ptr())
+        ctx.save_for_backward(h, wk, labels, count, coef)
+        ctx.param = w
+        ctx.cfg = (hs, dn)
+        ctx.mark_non_differentiable(count)
+        return out[1], count
+
+    @staticmethod
+    def backward(ctx, dloss, dcount):
+        h, wk, labels, count, coef = ctx.saved_tensors
+        if dloss is None or coef is None:
+            return None, None, None, None
+        hs, dn = ctx.cfg
+        T, D = h.shape
+        V = wk.shape[0]
+        dev = h.device
+        up = dloss.detach().to(torch.float32).reshape(1).contiguous()
+        w = ctx.param
+        direct = _param_grads_direct((w,))
+        dw = None
+        if direct:
+            dw = w.grad
+        elif ctx.needs_input_grad[1]:
+            dw = torch.empty(V, D, device=dev, dtype=torch.float32)
+        dh = torch.empty(T, D, device=dev, dtype=h.dtype) if ctx.needs_input_grad[0] else None
+        nws = N.lib().dna_lm_head_bwd_workspace(T, D, V) if dw is not None else 0
+        ws = torch.empty(max(nws // 4, 4), device=dev, dtype=torch.float32)
+        with _timed("lm_head_bwd", float(T) * D * h.element_size(), kind="byte"):
+            N.call("dna_lm_head_bwd", coef.data_ptr(), h.data_ptr(), hs, _dt(h), wk.data_ptr(),
+                   _dt(wk), labels.data_ptr(), count.data_ptr(), up.data_ptr(), dn, T, D, V,
+                   _p(dh), D, _p(dw), int(direct), ws.data_ptr(), ws.numel() * 4, N.stream_ptr())
+        if direct:
+            notify = getattr(w, "_dna_notify", None)
+            if notify is not None:
+                notify(w)
+            return dh, None, None, None
+        return dh, dw, None, None
+
+
+def masked_lm_head(h, weight, labels, denom=None):
+    """MaskedLMHead outside autocast (the kernels take h in its own dtype, so the result is the
+    same with and without it). h [..., D], labels [...] -> (loss, count)."""
+    with torch.autocast("cuda", enabled=False):
+        return MaskedLMHead.apply(h.reshape(-1, h.shape[-1]), weight, labels.reshape(-1), denom)
+
+
 # ----------------------------------------------------------------------------------- cls head
 CLS_PROBLEMS = {"regression": N.CLS_REGRESSION, "single_label_classification": N.CLS_SINGLE_LABEL,
                 "multi_label_classification": N.CLS_MULTI_LABEL}

@@ -14,6 +14,7 @@ torch ops.
 """
 import os
 from collections import namedtuple
+from dataclasses import dataclass
 from functools import partial
 
 import torch
@@ -247,6 +248,62 @@ class BertLMHeadModel(nn.Module):
         ids = input_ids[0]
         logits = self.lm_head(self.backbone(ids, position_ids=position_ids))
         return CausalLMOutput(logits=(logits, mask)), None
+
+    def mlm_loss(self, input_ids, mask, index, n_mask=None, n_unk_masked=None):
+        """The task loss bert_cross_entropy (src/tasks/metrics.py:268-273: mean CE over the masked
+        positions against the original ids) without dense [b, S, V] logits; BertForMaskedLM's
+        signature, with a BlmIndex as `index`. -> (loss, compact logits | None).
+
+        Padded vocabulary <= 64 (the character tokenizer): the backbone output goes to the fused
+        head (functional.MaskedLMHead, csrc/lm_head.hip) with index.labels; no logits exist, the
+        divisor is counted on the device. Larger vocabularies (BPE 4096): the masked rows are
+        compacted with index_select (as bert_layers.mlm_logits does), projected by the tied head
+        and scored by MaskedCrossEntropy over n_mask rows; the backward scatters them into a zero
+        [T, D]. A batch without a masked position gives loss 0 and zero gradients; the
+        reference's mean over an empty selection is NaN there. n_unk_masked is unused: this
+        model scores every masked row."""
+        h = self.backbone(input_ids)
+        w = self.lm_head.weight
+        V, D = w.shape
+        if V <= DF.LM_HEAD_MAX_VOCAB:
+            loss, _ = DF.masked_lm_head(h, w, index.labels)
+            return loss, None
+        M = int(index.flat_masked.numel())
+        if M == 0:
+            return h.sum() * 0.0, None
+        rows = h.reshape(-1, D).index_select(0, index.flat_masked)
+        logits = hip_linear(rows, w)
+        return DF.MaskedCrossEntropy.apply(logits, index.target, M), logits
+
+
+@dataclass
+class BlmIndex:
+    """Row bookkeeping of one masked-LM batch for BertLMHeadModel.mlm_loss, built on the host
+    while the batch is collated (no device sync in the step).
+
+    labels       [b * S] int64: the original id at the masked positions, -100 elsewhere
+    flat_masked  [M] flattened masked positions;  target [M]: the original ids at them
+    """
+    labels: torch.Tensor
+    flat_masked: torch.Tensor
+    target: torch.Tensor
+
+    @staticmethod
+    def build(mask, target, vocab_size=None):
+        mask = mask.reshape(-1).bool()
+        target = target.reshape(-1).to(torch.int64)
+        labels = torch.where(mask, target, torch.full_like(target, -100))
+        flat_masked = torch.nonzero(mask).flatten()
+        tgt = target[flat_masked]
+        if tgt.numel() and (int(tgt.min()) < 0 or
+                            (vocab_size is not None and int(tgt.max()) >= vocab_size)):
+            raise ValueError(f"masked-LM targets must lie in [0, {vocab_size}); got "
+                             f"[{int(tgt.min())}, {int(tgt.max())}]")
+        return BlmIndex(labels, flat_masked, tgt)
+
+    def to(self, device, non_blocking=False):
+        return BlmIndex(*(t.to(device, non_blocking=non_blocking)
+                          for t in (self.labels, self.flat_masked, self.target)))
 
 
 class DNAEmbeddingModel(nn.Module):

@@ -21,6 +21,8 @@ asserts (flash_attn_triton.py:849-855) -- instead of letting a kernel read out o
     torch.ops.dna_amd.pool_head_fwd(x1, x2, flip2, mirror2, start, count, w, bias, pooled, logits)
     torch.ops.dna_amd.pool_head_bwd(dlogits, pooled, w, start, count, dx1, dx2, flip2, mirror2, dw,
                                     dbias, accumulate)
+    torch.ops.dna_amd.lm_head_fwd(h, w, labels, denom, loss, count, coef)
+    torch.ops.dna_amd.lm_head_bwd(coef, h, w, labels, count, upstream, denom, dh, dw, accumulate)
 and the reference's FlashAttention kernel slot with its own signature (flash_attn_triton.py:
 1077-1130, called at bert_layers.py:188/192 as flash_attn_qkvpacked_func(qkv, bias)), autograd
 included:
@@ -516,7 +518,75 @@ def pool_head_bwd(dlogits: torch.Tensor, pooled: torch.Tensor, w: torch.Tensor,
            N.stream_ptr())
 
 
+def _lm_rows(name, x):
+    _check(x.is_cuda, f"{name} must be on the GPU (no CPU fallback), got {x.device}")
+    _check(x.dtype in _DT, f"{name} dtype {x.dtype} not in {tuple(_DT)}")
+    _check(x.dim() == 2 and x.numel() > 0, f"{name} must be a non-empty [T, D]")
+    T, D = x.shape
+    _check(x.stride(1) == 1 and (T == 1 or x.stride(0) >= D),
+           f"{name} must have unit column stride and a row stride >= D")
+    return x.stride(0) if T > 1 else D
+
+
+def _lm_common(w, labels, count, T, D):
+    V = w.shape[0]
+    _cuda_contig("w", w, tuple(_DT))
+    _check(tuple(w.shape) == (V, D) and 1 <= V <= 64, f"w must be [V <= 64, {D}], got {tuple(w.shape)}")
+    _cuda_contig("labels", labels, (torch.int64,))
+    _check(labels.numel() == T, f"labels must be int64 [{T}]")
+    _cuda_contig("count", count, (torch.int64,))
+    _check(count.numel() == 1, "count must hold one int64")
+    return V
+
+
+@torch.library.custom_op("dna_amd::lm_head_fwd", mutates_args=("loss", "count", "coef"))
+def lm_head_fwd(h: torch.Tensor, w: torch.Tensor, labels: torch.Tensor, denom: float,
+                loss: torch.Tensor, count: torch.Tensor, coef: torch.Tensor | None) -> None:
+    """Masked cross entropy of h w^T over the rows with 0 <= labels < V, no logits tensor:
+    loss[0] = the sum, loss[1] = sum / (denom > 0 ? denom : count) (0 when count == 0), count = the
+    kept rows, coef [T, V] = softmax - onehot on kept rows (the other rows are not written)."""
+    hs = _lm_rows("h", h)
+    T, D = h.shape
+    V = _lm_common(w, labels, count, T, D)
+    _cuda_contig("loss", loss, (torch.float32,))
+    _check(loss.numel() == 2, "loss must hold two fp32 values (sum, mean)")
+    if coef is not None:
+        _cuda_contig("coef", coef, (torch.float32,))
+        _check(tuple(coef.shape) == (T, V), f"coef must be [{T}, {V}]")
+    nws = N.lib().dna_lm_head_fwd_workspace(T)
+    ws = torch.empty(max(nws // 8, 2), device=h.device, dtype=torch.float64)
+    N.call("dna_lm_head_fwd", h.data_ptr(), hs, _DT[h.dtype], w.data_ptr(), _DT[w.dtype],
+           labels.data_ptr(), T, D, V, float(denom), loss.data_ptr(), count.data_ptr(),
+           loss.data_ptr() + 4, _p(coef), ws.data_ptr(), ws.numel() * 8, N.stream_ptr())
+
+
+@torch.library.custom_op("dna_amd::lm_head_bwd", mutates_args=("dh", "dw"))
+def lm_head_bwd(coef: torch.Tensor, h: torch.Tensor, w: torch.Tensor, labels: torch.Tensor,
+                count: torch.Tensor, upstream: torch.Tensor | None, denom: float,
+                dh: torch.Tensor, dw: torch.Tensor, accumulate: bool) -> None:
+    """Backward of lm_head_fwd: dh [T, D] in h's dtype (a view with unit column stride; every
+    element written, zeros on ignored rows) and dw [V, D] fp32 (accumulate: added into it), both
+    times upstream[0] / (denom > 0 ? denom : count)."""
+    hs = _lm_rows("h", h)
+    ds = _lm_rows("dh", dh)
+    T, D = h.shape
+    V = _lm_common(w, labels, count, T, D)
+    _check(dh.shape == h.shape and dh.dtype == h.dtype, "dh must match h")
+    for n, t, shape in (("coef", coef, (T, V)), ("dw", dw, (V, D))):
+        _cuda_contig(n, t, (torch.float32,))
+        _check(tuple(t.shape) == shape, f"{n} must be {shape}, got {tuple(t.shape)}")
+    if upstream is not None:
+        _cuda_contig("upstream", upstream, (torch.float32,))
+        _check(upstream.numel() == 1, "upstream must hold one fp32 value")
+    nws = N.lib().dna_lm_head_bwd_workspace(T, D, V)
+    ws = torch.empty(max(nws // 4, 4), device=h.device, dtype=torch.float32)
+    N.call("dna_lm_head_bwd", coef.data_ptr(), h.data_ptr(), hs, _DT[h.dtype], w.data_ptr(),
+           _DT[w.dtype], labels.data_ptr(), count.data_ptr(), _p(upstream), float(denom), T, D, V,
+           dh.data_ptr(), ds, dw.data_ptr(), int(accumulate), ws.data_ptr(), ws.numel() * 4,
+           N.stream_ptr())
+
+
 OPS = ("attn_fwd", "attn_bwd", "alibi_attn_qkvpacked", "flash_attn_qkvpacked", "linear_fwd",
        "transpose_bf16", "geglu_linear_fwd", "geglu_linear_dgrad",
        "geglu_fwd", "geglu_bwd", "xent_fwd", "cls_head_fwd", "cls_loss", "cls_head_bwd", "pool_head_fwd",
-       "pool_head_bwd")
+       "pool_head_bwd", "lm_head_fwd", "lm_head_bwd")

@@ -17,7 +17,7 @@ from .bert_layers import BertForMaskedLM, BertForSequenceClassification, MLMInde
 from .ddp import GradBucketReducer, broadcast_
 from .flat import FlatParams
 from .functional import LNFromYGuard
-from .optim import FusedAdamW, LinearLRSchedulerWarmup
+from .optim import SCHEDULERS, FusedAdamW, LinearLRSchedulerWarmup, ParamGroups
 
 
 @dataclass
@@ -65,7 +65,9 @@ class ModuleTrainer:
 
     def __init__(self, model, device, loss_fn, lr=1e-3, weight_decay=0.0, betas=(0.9, 0.999),
                  eps=1e-8, max_grad_norm=1.0, bucket_mb=25.0, wire_dtype="fp32",
-                 autocast=torch.bfloat16):
+                 autocast=torch.bfloat16, groups=None):
+        """groups: an optim.ParamGroups of `model` (opt-in): the flat buffers are laid out by it
+        and AdamW steps each `_optim` group with its own hyperparameters."""
         self.model = model.to(device).train()
         self.device = torch.device(device)
         self.loss_fn = loss_fn
@@ -74,7 +76,8 @@ class ModuleTrainer:
         # step, stands in for autocast's per-forward weight casts where the kernels read it
         # (mamba._lowp: `_dna_lp` on the parameter)
         lowp = autocast == torch.bfloat16 and torch.device(device).type == "cuda"
-        self.flat = FlatParams(self.model, device, shadow_dtype=torch.bfloat16 if lowp else None)
+        self.flat = FlatParams(self.model, device, shadow_dtype=torch.bfloat16 if lowp else None,
+                               group_of=groups)
         if lowp:
             for p in self.flat.params:
                 p._dna_lp = self.flat.lp(p)
@@ -82,7 +85,7 @@ class ModuleTrainer:
         # directly (no returned dW, no AccumulateGrad add); others return theirs as before
         self.flat.enable_direct_grad(True)
         self.opt = FusedAdamW(self.flat, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay,
-                              max_grad_norm=max_grad_norm)
+                              max_grad_norm=max_grad_norm, groups=groups)
         self.ln_guard = LNFromYGuard(self.flat, self.opt)
         self.reducer = GradBucketReducer(self.flat, bucket_mb=bucket_mb, wire_dtype=wire_dtype)
         self.world = self.reducer.world
@@ -140,9 +143,15 @@ class MLMTrainer:
         r = self.model.dropout_rng
         return {"seed": int(r.seed), "offset": int(r.offset)}
 
-    def load_rng_state(self, st):
-        self.model.dropout_rng.seed = int(st["seed"])
+    def load_rng_state(self, st, rank=0):
+        """rank: added to the saved seed (a checkpoint holds rank 0's stream; every rank draws
+        its own, as __init__ derives them)."""
+        self.model.dropout_rng.seed = (int(st["seed"]) + int(rank)) & (2 ** 63 - 1)
         self.model.dropout_rng.offset = int(st["offset"])
+
+    def device_batch(self, masked_ids, mask, labels, target, pad_token_id=3):
+        """Collated CPU tensors -> the batch `step` and the model's mlm_loss take."""
+        return DeviceBatch.from_host(masked_ids, mask, labels, target, self.device, pad_token_id)
 
     def step(self, batch, accum=None) -> torch.Tensor:
         """One optimizer step over one micro-batch or a list of them (accumulate_grad_batches:
@@ -329,3 +338,89 @@ class SeqClsTrainer(ModuleTrainer):
             return self.model.cls_logits(input_ids, labels)
         finally:
             self.model.train(was)
+
+
+class BlmTrainer(ModuleTrainer):
+    """Masked-LM pretraining step engine for hyena_lm.BertLMHeadModel (registry model "blm"):
+    ModuleTrainer's step -- flat fp32 parameters with the bf16 shadow under bf16 autocast,
+    gradient buckets all-reduced as the backward completes them, clip + AdamW fused -- with
+    MLMTrainer's interface, which train.py drives: step(batch | [micro-batches], accum), sched,
+    micro_losses, rng_state / load_rng_state, device_batch. The Hyena filter's parameters
+    (`_optim`: their own lr, no weight decay) step in AdamW groups of their own
+    (optim.ParamGroups). These models draw dropout from torch's generators, so that is the RNG
+    state kept; it is seeded with seed + rank. precision: autocast=torch.bfloat16 or None (fp32)."""
+
+    def __init__(self, model, device, lr=6e-4, weight_decay=0.1, betas=(0.9, 0.999), eps=1e-8,
+                 max_grad_norm=1.0, scheduler=None, scheduler_name="cosine_warmup_timm",
+                 bucket_mb=25.0, seed=None, wire_dtype="fp32", autocast=torch.bfloat16):
+        rank = dist.get_rank() if dist.is_initialized() else 0
+        if seed is not None:
+            torch.manual_seed(int(seed) + rank)
+        super().__init__(model, device, None, lr=lr, weight_decay=weight_decay, betas=betas,
+                         eps=eps, max_grad_norm=max_grad_norm, bucket_mb=bucket_mb,
+                         wire_dtype=wire_dtype, autocast=autocast, groups=ParamGroups(model))
+        self.sched = SCHEDULERS[scheduler_name](self.opt, **scheduler) if scheduler else None
+        self.vocab_size = int(self.model.lm_head.weight.shape[0])
+        self.micro_losses = []  # undivided loss of each micro-batch of the last step (metrics)
+
+    def rng_state(self):
+        st = {"cpu": torch.get_rng_state()}
+        if self.device.type == "cuda":
+            st["cuda"] = torch.cuda.get_rng_state(self.device)
+        return st
+
+    def load_rng_state(self, st, rank=0):
+        """A checkpoint holds rank 0's generator states; the other ranks keep the streams their
+        own seed gave them (distinct per rank, not replayed)."""
+        if rank:
+            return
+        torch.set_rng_state(st["cpu"])
+        if "cuda" in st and self.device.type == "cuda":
+            torch.cuda.set_rng_state(st["cuda"], self.device)
+
+    def device_batch(self, masked_ids, mask, labels, target, pad_token_id=None):
+        """Collated CPU tensors -> device batch; the head's labels (the original id at masked
+        positions, -100 elsewhere) and the masked rows are found on the host, where the targets
+        are also checked against the vocabulary (no GPU sync)."""
+        from .hyena_lm import BlmIndex
+        idx = BlmIndex.build(mask, target, self.vocab_size)
+        pin = lambda t: t.pin_memory() if torch.cuda.is_available() else t
+        dev = lambda t: pin(t).to(self.device, non_blocking=True)
+        return DeviceBatch(dev(masked_ids), dev(mask), dev(labels), dev(target),
+                           BlmIndex(dev(idx.labels), dev(idx.flat_masked), dev(idx.target)),
+                           int(idx.flat_masked.numel()), 0)
+
+    def _loss(self, mb):
+        if self.autocast is not None:
+            with torch.autocast(self.device.type, dtype=self.autocast):
+                return self.model.mlm_loss(mb.masked_ids, mb.mask, mb.index, mb.n_mask,
+                                           mb.n_unk_masked)[0]
+        return self.model.mlm_loss(mb.masked_ids, mb.mask, mb.index, mb.n_mask,
+                                   mb.n_unk_masked)[0]
+
+    def step(self, batch, accum=None) -> torch.Tensor:
+        """One optimizer step over one micro-batch or a list of them; MLMTrainer.step's
+        contract: each micro-batch loss is divided by `accum` (default their number), gradients
+        are all-reduced only during the last micro-batch's backward."""
+        micro = batch if isinstance(batch, (list, tuple)) else [batch]
+        div = len(micro) if accum is None else int(accum)
+        self._versions = _sync_shadow(self.flat, self._versions)
+        self.ln_guard.poll()
+        self.opt.zero_grad()
+        total = None
+        self.micro_losses = []
+        for i, mb in enumerate(micro):
+            self.reducer.prepare(sync=i == len(micro) - 1)
+            loss = self._loss(mb)
+            self.micro_losses.append(loss.detach())
+            if div > 1:
+                loss = loss / div
+            loss.backward()
+            total = loss.detach() if total is None else total + loss.detach()
+        self.reducer.finish()
+        self.opt.step(grad_scale=self.reducer.grad_scale)
+        if self.sched is not None:
+            self.sched.step()
+        self.ln_guard.launch()
+        self.global_step += 1
+        return total

@@ -23,6 +23,9 @@ extern "C" {
 #endif
 
 #define DNA_AMD_ABI_VERSION 1
+/* Counts additions that leave every version-1 entry point as it was (a caller built against an
+ * earlier revision keeps working): 1 = dna_lm_head_*. */
+#define DNA_AMD_ABI_REVISION 1
 
 enum dna_status {
   DNA_OK = 0,
@@ -37,6 +40,7 @@ enum dna_dtype { DNA_F32 = 0, DNA_BF16 = 1, DNA_F16 = 2 };
 enum dna_act { DNA_ACT_NONE = 0, DNA_ACT_GELU = 1 };
 
 int dna_abi_version(void);
+int dna_abi_revision(void);
 const char* dna_last_error(void);
 
 /* ------------------------------------------------------------------ attention (ALiBi + key pad)
@@ -604,6 +608,40 @@ int dna_pool_head_bwd(const float* dlogits, const float* upstream, const float* 
                       int width, int labels_n, int x_dtype, void* dx1, int64_t dx1_stride, void* dx2,
                       int64_t dx2_stride, int flip2, float* dW, float* dbias, int accumulate,
                       void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------ small-vocabulary masked-LM head
+ * The tied LM head + masked cross entropy of the HyenaDNA "blm" model (reference
+ * src/models/sequence/long_conv_lm.py:578-682 lm_head, src/tasks/metrics.py:268-273
+ * bert_cross_entropy) without a logits tensor, csrc/lm_head.hip. For h [T, D] (DNA_F32 or
+ * DNA_BF16, unit column stride, row r at h + r * h_stride elements), W [V, D] contiguous (the fp32
+ * master or its bf16 copy; no bias) and labels [T] int64 -- a row whose label is outside [0, V)
+ * is ignored and its h is never read:
+ *   logit_v = sum_d h[r, d] W[v, d] (fp32);  loss_sum = sum over kept rows of lse - logit_label
+ *   count = kept rows (device scalar);  loss = loss_sum / (denom > 0 ? denom : count), and 0
+ *   when count == 0 (the reference's mean over an empty selection is NaN)
+ *   coef [T, V] fp32 (may be NULL when no backward follows): softmax - onehot, kept rows only
+ *   written, what dna_lm_head_bwd reads
+ * dna_lm_head_bwd, with g = upstream[0] (a device scalar; NULL = 1) / (denom > 0 ? denom : count):
+ *   dh [T, D] in h_dtype with dh_stride: g sum_v coef[r, v] W[v, :] on kept rows, exact zeros on
+ *   the others; every element written once (never pre-zero it). dh == NULL: not computed.
+ *   dW [V, D] fp32 = g sum_r coef[r, v] h[r, :] (accumulate != 0: added into the buffer, which
+ *   also receives the embedding's gradient of the tied weight). dW == NULL: not computed.
+ *   count == 0: dh = 0, dW = 0 (unchanged under accumulate).
+ * 1 <= V <= 64, D >= 1, T >= 1. 16-byte accesses when D, the row stride and the pointers allow
+ * them, else element accesses in the same kernels. fp32 accumulation in a fixed order (the loss
+ * in double), no atomics, no hand-off between workgroups inside a launch: bit-identical from run
+ * to run. Forward 2 launches, backward 1 (dh) + 2 (dW). */
+size_t dna_lm_head_fwd_workspace(int rows);
+int dna_lm_head_fwd(const void* h, int64_t h_stride, int h_dtype, const void* W, int w_dtype,
+                    const int64_t* labels, int rows, int width, int vocab, float denom,
+                    float* loss_sum, int64_t* count, float* loss, float* coef, void* workspace,
+                    size_t workspace_bytes, void* stream);
+size_t dna_lm_head_bwd_workspace(int rows, int width, int vocab);
+int dna_lm_head_bwd(const float* coef, const void* h, int64_t h_stride, int h_dtype, const void* W,
+                    int w_dtype, const int64_t* labels, const int64_t* count,
+                    const float* upstream, float denom, int rows, int width, int vocab, void* dh,
+                    int64_t dh_stride, float* dW, int accumulate, void* workspace,
+                    size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------ optimizer (flat buffers)
  * Lightning gradient_clip_val=1.0 (torch.nn.utils.clip_grad_norm_) + torch AdamW

@@ -6,6 +6,9 @@ train() :668-694 -> Lightning fit) for the DNABERT-2 MLM path, without Hydra or 
   * config: dna_amd.compose (defaults lists, @package, overrides, eval/div_up resolvers);
     `--config-dir` may point at the reference's own configs/ tree, which composes unchanged;
   * registries: model "dnabert2" -> dna_amd.bert_layers.BertForMaskedLM (src/utils/registry.py:39),
+    model "blm" -> dna_amd.hyena_lm.BertLMHeadModel (HyenaDNA masked-LM pretraining: BlmTrainer,
+    the fused small-vocabulary head, `_optim` AdamW groups), schedulers "linear_warmup" and
+    "cosine_warmup_timm",
     dataset "bert_hg38" -> dna_amd.hg38.BertHG38, "dnabert2_pretrain" (text corpus) ->
     dna_amd.corpus.DNABERT2Pretrain, task "hg38" + loss "bert_cross_entropy";
   * loop: MLMTrainer steps (fused loss, bucketed RCCL all-reduce, clip + AdamW, LR schedule per
@@ -45,7 +48,11 @@ sys.path.insert(0, ROOT)
 
 from dna_amd.compose import compose  # noqa: E402
 
-MODEL_REGISTRY = {"dnabert2": "dna_amd.bert_layers.BertForMaskedLM"}
+MODEL_REGISTRY = {"dnabert2": "dna_amd.bert_layers.BertForMaskedLM",
+                  "blm": "dna_amd.hyena_lm.BertLMHeadModel"}
+# the step engine that goes with each registry model
+TRAINER_REGISTRY = {"dnabert2": "dna_amd.trainer.MLMTrainer", "blm": "dna_amd.trainer.BlmTrainer"}
+SCHEDULERS = ("linear_warmup", "cosine_warmup_timm")
 
 
 def _import(path):
@@ -53,9 +60,14 @@ def _import(path):
     return getattr(__import__(mod, fromlist=[name]), name)
 
 
-def _precision(p):
+def _precision(p, fp16_as_bf16=False):
     p = str(p)
     if p in ("bf16", "bf16-mixed", "bfloat16"):
+        return "bf16"
+    if fp16_as_bf16 and p in ("16", "16-mixed"):
+        # the reference's blm experiments ask for fp16 mixed precision on GPUs without bf16;
+        # the kernels here have bf16 and fp32 paths only
+        warnings.warn(f"trainer.precision={p}: running bf16 mixed precision (no fp16 path)")
         return "bf16"
     if p in ("32", "32-true", "fp32", "float32"):
         return "fp32"
@@ -69,6 +81,21 @@ def build_dataset(cfg):
           if k != "_name_" and not k.startswith("__")}  # process_config drops "__" keys
     ds = SequenceDataset.registry[cfg.dataset._name_](**kw)
     return ds
+
+
+def build_model(cfg, precision):
+    """The registry model of cfg.model. "dnabert2" takes its `config:` sub-key; "blm" is built
+    from cfg.model's own keys (the reference's blm block has no `config:`), and keys LMBackbone
+    refuses keep raising."""
+    name = cfg.model._name_
+    if name not in MODEL_REGISTRY:
+        raise KeyError(f"model._name_={name!r} is not in train.py's registry "
+                       f"({sorted(MODEL_REGISTRY)})")
+    model_cls = _import(MODEL_REGISTRY[name])
+    if name == "dnabert2":
+        return model_cls(config=cfg.model.config.to_container(), precision=precision)
+    kw = {k: v for k, v in cfg.model.to_container().items() if k != "_name_"}
+    return model_cls(**kw)
 
 
 def load_lightning_state(model, path, strict):
@@ -238,6 +265,16 @@ def eval_batches(n, limit):
     return min(n, max(0, int(limit)))
 
 
+def eval_loss(trainer, db):
+    """The model's mlm_loss on one device batch, under the trainer's autocast when it has one."""
+    ac = getattr(trainer, "autocast", None)
+    if ac is not None:
+        with torch.autocast("cuda", dtype=ac):
+            return trainer.model.mlm_loss(db.masked_ids, db.mask, db.index, db.n_mask,
+                                          db.n_unk_masked)[0]
+    return trainer.model.mlm_loss(db.masked_ids, db.mask, db.index, db.n_mask, db.n_unk_masked)[0]
+
+
 def evaluate(trainer, loaders, device, pad_id, limit=1.0, tokens=None):
     """validation_step / test_step through _shared_step (train.py:339-380, 442-460) for the MLM
     task: forward-only on the training kernels in eval mode (dropout off), the task loss
@@ -251,6 +288,10 @@ def evaluate(trainer, loaders, device, pad_id, limit=1.0, tokens=None):
     from dna_amd.ddp import reduce_metrics
     from dna_amd.trainer import DeviceBatch
     model = trainer.model
+    # the trainer's own batch builder (blm: the fused head's labels); anything else that only
+    # carries `.model` gets the DNABERT-2 batch
+    make_batch = getattr(trainer, "device_batch", None) or (
+        lambda *a: DeviceBatch.from_host(*a[:4], device, a[4]))
     was_training = model.training
     model.eval()
     tokens = tokens if tokens is not None else {}
@@ -265,9 +306,8 @@ def evaluate(trainer, loaders, device, pad_id, limit=1.0, tokens=None):
                 for bi, ((masked, mask, labels), target) in enumerate(loader):
                     if bi >= n:
                         break
-                    db = DeviceBatch.from_host(masked, mask, labels, target, device, pad_id)
-                    loss, _ = model.mlm_loss(db.masked_ids, db.mask, db.index, db.n_mask,
-                                             db.n_unk_masked)
+                    db = make_batch(masked, mask, labels, target, pad_id)
+                    loss = eval_loss(trainer, db)
                     bs, numel = int(target.shape[0]), int(target.numel())
                     loss_w += loss.double() * bs
                     nll += loss.double() * numel
@@ -297,7 +337,6 @@ def evaluate(trainer, loaders, device, pad_id, limit=1.0, tokens=None):
 def train(cfg, dry_run=False, out=sys.stdout):
     from dna_amd.bert_layers import BertForMaskedLM  # noqa: F401
     from dna_amd.ddp import reduce_metrics
-    from dna_amd.trainer import DeviceBatch, MLMTrainer
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -310,9 +349,9 @@ def train(cfg, dry_run=False, out=sys.stdout):
     if str(tr.get("accelerator", "gpu")) not in ("gpu", "cuda", "auto"):
         raise RuntimeError(f"trainer.accelerator={tr.accelerator!r}: dna_amd runs the hot path "
                            "on MI355X GPUs only (no CPU fallback)")
-    model_cls = _import(MODEL_REGISTRY[cfg.model._name_])
-    model = model_cls(config=cfg.model.config.to_container(),
-                      precision=_precision(tr.get("precision", "bf16")))
+    is_blm = cfg.model._name_ == "blm"
+    precision = _precision(tr.get("precision", "bf16"), fp16_as_bf16=is_blm)
+    model = build_model(cfg, precision)
     pre = cfg.train.get("pretrained_model_path")
     if pre:
         if os.path.exists(pre):
@@ -326,14 +365,21 @@ def train(cfg, dry_run=False, out=sys.stdout):
     sched = None
     if "scheduler" in cfg and cfg.scheduler is not None:
         sc = {k: v for k, v in cfg.scheduler.to_container().items() if k != "_name_"}
-        if cfg.scheduler._name_ != "linear_warmup":
-            raise NotImplementedError(f"scheduler {cfg.scheduler._name_!r} (linear_warmup only)")
+        if cfg.scheduler._name_ not in SCHEDULERS or \
+                (cfg.scheduler._name_ != "linear_warmup" and not is_blm):
+            raise NotImplementedError(f"scheduler {cfg.scheduler._name_!r} "
+                                      f"({', '.join(SCHEDULERS)}; dnabert2: linear_warmup only)")
         sched = sc
     opt = cfg.optimizer
     if dry_run:
-        print(json.dumps({"dry_run": True, "model_params": sum(p.numel() for p in model.parameters()),
-                          "train_windows": len(ds.dataset_train), "task": task.loss_name,
-                          "scheduler": sched, "optimizer": opt.to_container()}), file=out)
+        info = {"dry_run": True, "model_params": sum(p.numel() for p in model.parameters()),
+                "train_windows": len(ds.dataset_train), "task": task.loss_name,
+                "scheduler": sched, "optimizer": opt.to_container()}
+        if is_blm:
+            from dna_amd.optim import ParamGroups
+            info.update(model=cfg.model._name_, scheduler_name=cfg.scheduler._name_ if sched else None,
+                        param_groups=len(ParamGroups(model)))
+        print(json.dumps(info), file=out)
         return None
 
     want = n_devices(tr)
@@ -359,11 +405,16 @@ def train(cfg, dry_run=False, out=sys.stdout):
         print(json.dumps(dict({"event": "params"}, **params_log(model, ck_cfg.params))),
               file=out, flush=True)
     wire = str(tr.get("grad_wire", "fp32") or "fp32")
-    trainer = MLMTrainer(model, device, lr=float(opt.lr),
-                         weight_decay=float(opt.get("weight_decay", 0.0)),
-                         betas=tuple(opt.get("betas", (0.9, 0.999))),
-                         max_grad_norm=float(tr.get("gradient_clip_val", 0.0) or 0.0),
-                         scheduler=sched, seed=seed, wire_dtype=wire)
+    trainer_kw = dict(lr=float(opt.lr), weight_decay=float(opt.get("weight_decay", 0.0)),
+                      betas=tuple(opt.get("betas", (0.9, 0.999))),
+                      max_grad_norm=float(tr.get("gradient_clip_val", 0.0) or 0.0),
+                      scheduler=sched, seed=seed, wire_dtype=wire)
+    if is_blm:
+        trainer_kw.update(scheduler_name=cfg.scheduler._name_ if sched else None,
+                          autocast=torch.bfloat16 if precision == "bf16" else None)
+        if opt.get("eps") is not None:
+            trainer_kw["eps"] = float(opt.eps)
+    trainer = _import(TRAINER_REGISTRY[cfg.model._name_])(model, device, **trainer_kw)
     resume = tr.get("resume_from_checkpoint") or cfg.train.get("ckpt")
     start_epoch, skip_batches, restored = 0, 0, {}
     if resume:
@@ -379,9 +430,7 @@ def train(cfg, dry_run=False, out=sys.stdout):
             start_epoch = int(ck.get("epoch", 0))
             extra = ck.get("dna_amd") or {}
             if extra.get("dropout_rng"):
-                trainer.load_rng_state(extra["dropout_rng"])
-                # distinct per rank, as MLMTrainer derives it
-                trainer.model.dropout_rng.seed = (trainer.model.dropout_rng.seed + rank) & (2 ** 63 - 1)
+                trainer.load_rng_state(extra["dropout_rng"], rank=rank)  # distinct per rank
             skip_batches = int(extra.get("batches_done", 0))
             restored = extra.get("metrics") or {}
             if "batches_done" not in extra and "loops" in ck and \
@@ -543,7 +592,7 @@ def train(cfg, dry_run=False, out=sys.stdout):
                 break
             if bi < skip_batches:  # mid-epoch resume: these batches were consumed before
                 continue
-            micro.append((DeviceBatch.from_host(masked, mask, labels, target, device, pad_id),
+            micro.append((trainer.device_batch(masked, mask, labels, target, pad_id),
                           target.numel()))
             if len(micro) < accum:
                 continue
