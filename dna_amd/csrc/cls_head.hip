@@ -17,6 +17,7 @@
 
 #include <type_traits>
 
+#include "cls_loss.h"
 #include "common.h"
 
 namespace dna {
@@ -186,16 +187,9 @@ struct LossArgs {
 };
 
 // One workgroup: first the logits (an element per thread), then, behind a workgroup barrier, the
-// loss with a thread per row (b = tid, tid + 1024, ...). Row losses are added in double, per thread
-// in row order and then over the threads by a fixed tree.
-// pool_head.hip's loss_kernel restates the three losses with the row arithmetic in double: a
-// change to the label, tie or out-of-range rules here belongs there too.
+// loss with a thread per row and the row arithmetic in float (cls_loss.h).
 __global__ __launch_bounds__(1024) void finish_loss_kernel(LossArgs g) {
-  __shared__ double red[1024];
   const int tid = threadIdx.x, B = g.B, C = g.C;
-  const double inv_n = 1.0 / (g.problem == DNA_CLS_SINGLE_LABEL ? (double)B : (double)B * C);
-  const float inv_nf = (float)inv_n;
-  double acc = 0.0;
   if (g.part) {
     // logits = bc + the column tiles' partial sums, in tile order; one element per thread and
     // pass, the loads of a group of tiles in flight together
@@ -209,49 +203,7 @@ __global__ __launch_bounds__(1024) void finish_loss_kernel(LossArgs g) {
     if (!g.labels) return;
     __syncthreads();  // the rows below are read by other threads of this workgroup
   }
-  for (int b = tid; b < B; b += 1024) {
-    const float* lg = g.logits + (size_t)b * C;
-    float* dl = g.dlogits + (size_t)b * C;
-    if (g.problem == DNA_CLS_SINGLE_LABEL) {
-      float m = lg[0];
-      int arg = 0;
-      for (int c = 1; c < C; ++c) {
-        const float v = lg[c];
-        if (v > m) { m = v; arg = c; }  // strict: a tie keeps the lowest index
-      }
-      float s = 0.f;
-      for (int c = 0; c < C; ++c) s += expf(lg[c] - m);
-      const float lse = m + logf(s);
-      const long y = (long)reinterpret_cast<const int64_t*>(g.labels)[b];
-      const bool ok = y >= 0 && y < C;
-      acc += (double)(lse - (ok ? lg[y] : 0.f));
-      for (int c = 0; c < C; ++c) dl[c] = (expf(lg[c] - lse) - (c == y ? 1.f : 0.f)) * inv_nf;
-      if (g.pred) g.pred[b] = arg;
-    } else {
-      const float* y = reinterpret_cast<const float*>(g.labels) + (size_t)b * C;
-      for (int c = 0; c < C; ++c) {
-        const float v = lg[c], yc = y[c];
-        if (g.problem == DNA_CLS_REGRESSION) {
-          const float d = v - yc;
-          acc += (double)d * (double)d;
-          dl[c] = 2.f * d * inv_nf;
-        } else {  // BCE with logits: max(v, 0) - v y + log1p(exp(-|v|))
-          const float e = expf(-fabsf(v));
-          acc += (double)(fmaxf(v, 0.f) - v * yc + log1pf(e));
-          const float sig = v >= 0.f ? 1.f / (1.f + e) : e / (1.f + e);
-          dl[c] = (sig - yc) * inv_nf;
-        }
-      }
-    }
-  }
-  if (!g.labels) return;
-  red[tid] = acc;
-  __syncthreads();
-  for (int s = 512; s > 0; s >>= 1) {
-    if (tid < s) red[tid] += red[tid + s];
-    __syncthreads();
-  }
-  if (tid == 0) g.loss[0] = (float)(red[0] * inv_n);
+  cls_loss<float>(g.logits, g.labels, g.problem, B, C, g.loss, g.dlogits, g.pred);
 }
 
 // ------------------------------------------------------------------------------------ backward
@@ -404,8 +356,6 @@ static Prob make_prob(const float* L, long l_red, long l_i, const void* R, int r
 
 static int pool_ct(int B) { return ((B + RT - 1) / RT) * 4 >= 64 ? 64 : 16; }
 
-static bool aligned(const void* p, size_t n) { return ((uintptr_t)p & (n - 1)) == 0; }
-
 }  // namespace cls
 }  // namespace dna
 
@@ -420,7 +370,7 @@ using namespace dna;
   DNA_CHECK_ARG(x_dtype == DNA_F32 || x_dtype == DNA_BF16, name ": x must be fp32 or bf16");   \
   DNA_CHECK_ARG(x_row_stride >= H && x_row_stride % 4 == 0,                                    \
                 name ": x row stride must be >= H and a multiple of 4 (got %ld)", (long)x_row_stride); \
-  DNA_CHECK_ARG(cls::aligned(x, x_dtype == DNA_BF16 ? 8 : 16), name ": x must be 16-byte aligned")
+  DNA_CHECK_ARG(aligned(x, x_dtype == DNA_BF16 ? 8 : 16), name ": x must be 16-byte aligned")
 
 extern "C" size_t dna_cls_head_fwd_workspace(int B, int H, int C) {
   if (B < 1 || H < 64 || C < 1) return 0;
@@ -444,8 +394,8 @@ extern "C" int dna_cls_head_fwd(const void* x, int x_dtype, int64_t x_row_stride
                                 size_t workspace_bytes, void* stream) {
   DNA_CHECK_ARG(x && Wp && bp && Wc && bc && t && a && logits, "dna_cls_head_fwd: null pointer");
   DNA_CLS_SHAPE_CHECK("dna_cls_head_fwd");
-  DNA_CHECK_ARG(cls::aligned(Wp, 16) && cls::aligned(Wc, 16) && cls::aligned(t, 16) &&
-                    cls::aligned(a, 16),
+  DNA_CHECK_ARG(aligned(Wp, 16) && aligned(Wc, 16) && aligned(t, 16) &&
+                    aligned(a, 16),
                 "dna_cls_head_fwd: Wp / Wc / t / a must be 16-byte aligned");
   if (labels) {
     int st = cls_loss_check("dna_cls_head_fwd", problem_type, labels, loss, dlogits);
@@ -511,8 +461,8 @@ extern "C" int dna_cls_head_bwd(const float* dlogits, const float* upstream, con
   DNA_CHECK_ARG(dlogits && x && t && a && Wp && Wc && dWc && dbc && dWp && dbp && dx,
                 "dna_cls_head_bwd: null pointer");
   DNA_CLS_SHAPE_CHECK("dna_cls_head_bwd");
-  DNA_CHECK_ARG(cls::aligned(Wp, 16) && cls::aligned(Wc, 16) && cls::aligned(t, 16) &&
-                    cls::aligned(a, 16) && cls::aligned(workspace, 16),
+  DNA_CHECK_ARG(aligned(Wp, 16) && aligned(Wc, 16) && aligned(t, 16) &&
+                    aligned(a, 16) && aligned(workspace, 16),
                 "dna_cls_head_bwd: Wp / Wc / t / a / workspace must be 16-byte aligned");
   const size_t need = dna_cls_head_bwd_workspace(B, H, C);
   DNA_CHECK_ARG(workspace && workspace_bytes >= need,

@@ -219,4 +219,7 @@ __device__ __forceinline__ float wave_max(float v) {
 
 inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 
+// p is a multiple of n bytes (n a power of two)
+inline bool aligned(const void* p, size_t n) { return ((uintptr_t)p & (n - 1)) == 0; }
+
 }  // namespace dna

@@ -364,8 +364,6 @@ __global__ __launch_bounds__(TPB) void dw_finish_kernel(const float* part, int n
   dW[idx] = accumulate ? dW[idx] + s * scale : s * scale;
 }
 
-static bool aligned(const void* p, size_t n) { return ((uintptr_t)p & (n - 1)) == 0; }
-
 // pool_head.hip's rule: 16-byte accesses when D, the row stride and the base pointers allow
 // them (the rows of the contiguous W are then 16-byte aligned in either dtype), else one element
 static int pick_vec(int dtype, int D, const void* p, int64_t stride, const void* W) {
@@ -438,7 +436,7 @@ extern "C" int dna_lm_head_fwd(const void* h, int64_t h_stride, int h_dtype, con
   DNA_CHECK_ARG(h && W && labels && loss_sum && count, "dna_lm_head_fwd: null pointer");
   DNA_CHECK_ARG(h_stride >= D, "dna_lm_head_fwd: row stride must be >= D");
   const size_t need = dna_lm_head_fwd_workspace(T);
-  DNA_CHECK_ARG(workspace && workspace_bytes >= need && lmh::aligned(workspace, 8),
+  DNA_CHECK_ARG(workspace && workspace_bytes >= need && aligned(workspace, 8),
                 "dna_lm_head_fwd: workspace too small or not 8-byte aligned (%zu < %zu)",
                 workspace_bytes, need);
   hipStream_t s = as_stream(stream);

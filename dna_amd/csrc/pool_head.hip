@@ -24,6 +24,7 @@
 // Backward: grad_kernel (g, dW, dbias), then bcast_kernel writes every element of dx once.
 #include <type_traits>
 
+#include "cls_loss.h"
 #include "common.h"
 
 namespace dna {
@@ -258,63 +259,12 @@ __global__ __launch_bounds__(1024) void finish_kernel(FinArgs g) {
 }
 
 // ------------------------------------------------------------------------------- forward: loss
-struct LossArgs {
-  const float* logits; const void* labels; int problem; int B, C;
-  float* loss; float* dlogits; int64_t* pred;
-};
-
-// dna_cls_loss's three losses (same labels, same outputs, same tie rule for pred), one workgroup,
-// a thread per row, with the row's arithmetic in double: a batch of a few rows leaves dlogits of
-// magnitude 1 / B whose column sums (dbias) cancel to far smaller values, so dlogits carries its
-// one rounding to fp32 and nothing else. B x C elements: the cost is not measurable.
-__global__ __launch_bounds__(1024) void loss_kernel(LossArgs g) {
-  __shared__ double red[1024];
-  const int tid = threadIdx.x, B = g.B, C = g.C;
-  const double inv_n = 1.0 / (g.problem == DNA_CLS_SINGLE_LABEL ? (double)B : (double)B * C);
-  double acc = 0.0;
-  for (int b = tid; b < B; b += 1024) {
-    const float* lg = g.logits + (int64_t)b * C;
-    float* dl = g.dlogits + (int64_t)b * C;
-    if (g.problem == DNA_CLS_SINGLE_LABEL) {
-      float m = lg[0];
-      int arg = 0;
-      for (int c = 1; c < C; ++c) {
-        const float v = lg[c];
-        if (v > m) { m = v; arg = c; }  // strict: a tie keeps the lowest index
-      }
-      double s = 0.0;
-      for (int c = 0; c < C; ++c) s += exp((double)lg[c] - (double)m);
-      const double lse = (double)m + log(s);
-      const long y = (long)reinterpret_cast<const int64_t*>(g.labels)[b];
-      const bool ok = y >= 0 && y < C;
-      acc += lse - (ok ? (double)lg[y] : 0.0);
-      for (int c = 0; c < C; ++c)
-        dl[c] = (float)((exp((double)lg[c] - lse) - (c == y ? 1.0 : 0.0)) * inv_n);
-      if (g.pred) g.pred[b] = arg;
-    } else {
-      const float* y = reinterpret_cast<const float*>(g.labels) + (int64_t)b * C;
-      for (int c = 0; c < C; ++c) {
-        const double v = lg[c], yc = y[c];
-        if (g.problem == DNA_CLS_REGRESSION) {
-          const double d = v - yc;
-          acc += d * d;
-          dl[c] = (float)(2.0 * d * inv_n);
-        } else {  // BCE with logits: max(v, 0) - v y + log1p(exp(-|v|))
-          const double e = exp(-fabs(v));
-          acc += fmax(v, 0.0) - v * yc + log1p(e);
-          const double sig = v >= 0.0 ? 1.0 / (1.0 + e) : e / (1.0 + e);
-          dl[c] = (float)((sig - yc) * inv_n);
-        }
-      }
-    }
-  }
-  red[tid] = acc;
-  __syncthreads();
-  for (int s = 512; s > 0; s >>= 1) {
-    if (tid < s) red[tid] += red[tid + s];
-    __syncthreads();
-  }
-  if (tid == 0) g.loss[0] = (float)(red[0] * inv_n);
+// dna_cls_loss's three losses (same labels, same outputs, same tie rule for pred) with the row
+// arithmetic in double (cls_loss.h), one workgroup
+__global__ __launch_bounds__(1024) void loss_kernel(const float* logits, const void* labels,
+                                                    int problem, int B, int C, float* loss,
+                                                    float* dlogits, int64_t* pred) {
+  cls_loss<double>(logits, labels, problem, B, C, loss, dlogits, pred);
 }
 
 // ------------------------------------------------------------------------------------ backward
@@ -410,8 +360,6 @@ __global__ __launch_bounds__(TPB) void bcast_kernel(BcastArgs g) {
   }
 }
 
-static bool aligned(const void* p, size_t n) { return ((uintptr_t)p & (n - 1)) == 0; }
-
 // 16-byte accesses when D, the strides and the base pointers allow them, else one element
 static int pick_vec(int dtype, int D, const void* p1, int64_t s1, const void* p2, int64_t s2) {
   const int v = dtype == DNA_BF16 ? 8 : 4;
@@ -459,7 +407,7 @@ extern "C" int dna_pool_head_fwd(const void* x1, int64_t x1_stride, const void* 
   DNA_CHECK_ARG(x1_stride >= D && (!x2 || x2_stride >= D),
                 "dna_pool_head_fwd: position strides must be >= D");
   const size_t need = dna_pool_head_fwd_workspace(B, L, D);
-  DNA_CHECK_ARG(workspace && workspace_bytes >= need && pool::aligned(workspace, 16),
+  DNA_CHECK_ARG(workspace && workspace_bytes >= need && aligned(workspace, 16),
                 "dna_pool_head_fwd: workspace too small or not 16-byte aligned (%zu < %zu)",
                 workspace_bytes, need);
   hipStream_t s = as_stream(stream);
@@ -485,8 +433,8 @@ extern "C" int dna_pool_head_fwd(const void* x1, int64_t x1_stride, const void* 
   hipLaunchKernelGGL(pool::finish_kernel, dim3((unsigned)B), dim3(1024), 0, s, fa);
   DNA_LAUNCH_CHECK("dna_pool_head_fwd");
   if (labels) {
-    pool::LossArgs la{logits, labels, problem_type, B, C, loss, dlogits, pred};
-    hipLaunchKernelGGL(pool::loss_kernel, dim3(1), dim3(1024), 0, s, la);
+    hipLaunchKernelGGL(pool::loss_kernel, dim3(1), dim3(1024), 0, s, logits, labels, problem_type,
+                       B, C, loss, dlogits, pred);
     DNA_LAUNCH_CHECK("dna_pool_head_fwd");
   }
   return DNA_OK;

@@ -319,6 +319,15 @@ def _param_grads_direct(params):
                             for q in ps)
 
 
+def _notify_direct(*params):
+    """After a kernel has added its gradients straight into the .grad views of these parameters
+    (None entries skipped): tell whoever counts their contributions (ddp.GradBucketReducer)."""
+    for q in params:
+        notify = getattr(q, "_dna_notify", None) if q is not None else None
+        if notify is not None:
+            notify(q)
+
+
 class FusedLayerNorm(torch.autograd.Function):
     """LN(dropout(act(x + bias)) + residual) -> (y fp32|None, y_bf16|None).
 
@@ -416,10 +425,7 @@ class FusedLayerNorm(torch.autograd.Function):
                    rstd.data_ptr(), n, d, _p(dres), dx.data_ptr(), dg.data_ptr(), db.data_ptr(),
                    _p(dbias), ws.data_ptr(), nws, N.stream_ptr())
         if direct:
-            for q in ctx.params:
-                notify = getattr(q, "_dna_notify", None) if q is not None else None
-                if notify is not None:
-                    notify(q)
+            _notify_direct(*ctx.params)
             return dx, None, dres, None, None, None, None, None, None, None, None, None
         return dx, dbias, dres, dg, db, None, None, None, None, None, None, None
 
@@ -866,9 +872,7 @@ class MaskedLMHead(torch.autograd.Function):
                    _dt(wk), labels.data_ptr(), count.data_ptr(), up.data_ptr(), dn, T, D, V,
                    _p(dh), D, _p(dw), int(direct), ws.data_ptr(), ws.numel() * 4, N.stream_ptr())
         if direct:
-            notify = getattr(w, "_dna_notify", None)
-            if notify is not None:
-                notify(w)
+            _notify_direct(w)
             return dh, None, None, None
         return dh, dw, None, None
 
@@ -912,6 +916,36 @@ def _f32_param(name, t, shape):
                         f"{t.dtype} {tuple(t.shape)}")
 
 
+def _loss_outputs(labels, problem, logits):
+    """What the loss of a classification head reads and writes -> (labels as the kernel takes
+    them, loss [1], dlogits [B, C], pred [B] int64 | None: single-label only); all None without
+    labels."""
+    if labels is None:
+        return None, None, None, None
+    B, C = logits.shape
+    labels = _cls_labels(labels, problem, B, C)
+    loss = torch.empty(1, device=logits.device, dtype=torch.float32)
+    dl = torch.empty_like(logits)
+    pred = None
+    if problem == N.CLS_SINGLE_LABEL:
+        pred = torch.empty(B, device=logits.device, dtype=torch.int64)
+    return labels, loss, dl, pred
+
+
+def _logits_grad(dl, dlogits, dloss):
+    """What a classification head's backward starts from: dl, the dlogits its loss kernel stored
+    in the forward (None without labels), the incoming gradient of the logits and that of the
+    loss -> (g [B, C] fp32, up): the backward kernels take g * up[0], up None meaning 1, so the
+    loss's scalar gradient stays on the device. None: no gradient came in."""
+    if dl is not None and dloss is not None:
+        if dlogits is None:  # the usual case: only the loss was used
+            return dl, dloss.detach().to(torch.float32).reshape(1).contiguous()
+        return (dl * dloss + dlogits).contiguous(), None
+    if dlogits is not None:
+        return dlogits.to(torch.float32).contiguous(), None
+    return None
+
+
 class ClsHead(torch.autograd.Function):
     """BertPooler + dropout + classifier (+ loss) of BertForSequenceClassification (reference
     bert_layers.py:495-510, :969-998) on csrc/cls_head.hip:
@@ -939,13 +973,7 @@ class ClsHead(torch.autograd.Function):
         t = torch.empty(B, H, device=dev, dtype=torch.float32)
         a = torch.empty_like(t)
         logits = torch.empty(B, C, device=dev, dtype=torch.float32)
-        loss = dl = pred = None
-        if labels is not None:
-            labels = _cls_labels(labels, problem, B, C)
-            loss = torch.empty(1, device=dev, dtype=torch.float32)
-            dl = torch.empty_like(logits)
-            if problem == N.CLS_SINGLE_LABEL:
-                pred = torch.empty(B, device=dev, dtype=torch.int64)
+        labels, loss, dl, pred = _loss_outputs(labels, problem, logits)
         nws = N.lib().dna_cls_head_fwd_workspace(B, H, C)
         ws = torch.empty(max(nws // 4, 4), device=dev, dtype=torch.float32)
         with _timed("cls_head_fwd", 2.0 * B * H * (H + C)):
@@ -964,16 +992,10 @@ class ClsHead(torch.autograd.Function):
     def backward(ctx, dlogits, dloss, dpred):
         x, wp, wc, t, a, dl = ctx.saved_tensors
         stride, p, seed, off = ctx.cfg
-        up = None
-        if dl is not None and dloss is not None:
-            if dlogits is None:  # the usual case: only the loss was used
-                g, up = dl, dloss.detach().to(torch.float32).reshape(1).contiguous()
-            else:
-                g = (dl * dloss + dlogits).contiguous()
-        elif dlogits is not None:
-            g = dlogits.to(torch.float32).contiguous()
-        else:
+        g_up = _logits_grad(dl, dlogits, dloss)
+        if g_up is None:
             return (None,) * 10
+        g, up = g_up
         B, H = x.shape
         C = wc.shape[0]
         dev = x.device
@@ -994,10 +1016,7 @@ class ClsHead(torch.autograd.Function):
                    int(direct), ws.data_ptr(), ws.numel() * 4, N.stream_ptr())
         dx = dx if x.dtype == torch.float32 else dx.to(x.dtype)
         if direct:
-            for q in ctx.params:
-                notify = getattr(q, "_dna_notify", None)
-                if notify is not None:
-                    notify(q)
+            _notify_direct(*ctx.params)
             return (dx,) + (None,) * 9
         return dx, dwp, dbp, dwc, dbc, None, None, None, None, None
 
@@ -1122,13 +1141,7 @@ class PoolHead(torch.autograd.Function):
         count = _pool_window("count", count, B)
         pooled = torch.empty(B, D, device=dev, dtype=torch.float32)
         logits = torch.empty(B, C, device=dev, dtype=torch.float32)
-        loss = dl = pred = None
-        if labels is not None:
-            labels = _cls_labels(labels, problem, B, C)
-            loss = torch.empty(1, device=dev, dtype=torch.float32)
-            dl = torch.empty_like(logits)
-            if problem == N.CLS_SINGLE_LABEL:
-                pred = torch.empty(B, device=dev, dtype=torch.int64)
+        labels, loss, dl, pred = _loss_outputs(labels, problem, logits)
         nws = N.lib().dna_pool_head_fwd_workspace(B, L, D)
         ws = torch.empty(max(nws // 4, 4), device=dev, dtype=torch.float32)
         nin = 1 if xb is None else 2
@@ -1148,16 +1161,10 @@ class PoolHead(torch.autograd.Function):
     def backward(ctx, dlogits, dloss, dpred):
         w, pooled, dl, start, count = ctx.saved_tensors
         shape, dtype, D, rcps, two, flags = ctx.cfg
-        up = None
-        if dl is not None and dloss is not None:
-            if dlogits is None:  # the usual case: only the loss was used
-                g, up = dl, dloss.detach().to(torch.float32).reshape(1).contiguous()
-            else:
-                g = (dl * dloss + dlogits).contiguous()
-        elif dlogits is not None:
-            g = dlogits.to(torch.float32).contiguous()
-        else:
+        g_up = _logits_grad(dl, dlogits, dloss)
+        if g_up is None:
             return (None,) * 11
+        g, up = g_up
         B, L, W = shape
         C = w.shape[0]
         dev = w.device
@@ -1191,10 +1198,7 @@ class PoolHead(torch.autograd.Function):
                    flags, dw.data_ptr(), _p(db), int(direct), ws.data_ptr(), ws.numel() * 4,
                    N.stream_ptr())
         if direct:
-            for q in ctx.params:
-                notify = getattr(q, "_dna_notify", None) if q is not None else None
-                if notify is not None:
-                    notify(q)
+            _notify_direct(*ctx.params)
             return (dx, dx2) + (None,) * 9
         return dx, dx2, dw, db, None, None, None, None, None, None, None
 
@@ -1333,9 +1337,7 @@ def bias_grad(dy, bias=None):
             N.call("dna_colsum_bf16", dy.data_ptr(), rows, cols, out.data_ptr(), int(direct),
                    ws.data_ptr(), nws, N.stream_ptr())
         if direct:
-            notify = getattr(bias, "_dna_notify", None)
-            if notify is not None:
-                notify(bias)
+            _notify_direct(bias)
             return None
         return out
     return dy.sum(0, dtype=torch.float32)
@@ -1642,18 +1644,14 @@ def _weight_grad(w, dy, x, flops):
         with torch.cuda.stream(side), _timed("gemm_wgrad", flops):
             wgrad_accumulate(dy, x, w.grad)
         _queue_join()
-        notify = getattr(w, "_dna_notify", None)
-        if notify is not None:
-            notify(w)
+        _notify_direct(w)
         return None
     with _timed("gemm_wgrad", flops):
         if direct:
             # write straight into the flat fp32 gradient buffer (dna_amd.flat) and tell the
             # gradient-bucket reducer, instead of returning dW to AccumulateGrad
             wgrad_accumulate(dy, x, w.grad)
-            notify = getattr(w, "_dna_notify", None)
-            if notify is not None:
-                notify(w)
+            _notify_direct(w)
             return None
         return wgrad(dy, x)
 

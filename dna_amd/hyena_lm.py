@@ -340,7 +340,8 @@ def load_backbone(model, state_dict, freeze_backbone=False, ignore_head=True):
     "head" (with ignore_head) or "decoder" keep the fresh model's values, the rest are loaded;
     freeze_backbone turns off requires_grad on all of the model's parameters (a decoder outside it
     stays trainable). -> the keys that kept their fresh values."""
-    sd = {(k[len("model."):] if k.startswith("model.") else k): v for k, v in state_dict.items()}
+    from .trainer import strip_model_prefix
+    sd = strip_model_prefix(state_dict)
     own = model.state_dict()
     kept, new = [], {}
     for key in sorted(own):

@@ -113,7 +113,8 @@ def load_pretrained(model, state_dict, freeze_backbone=False):
     model.* and decoder.0.*: everything loaded, strictly). A Caduceus classifier loads whatever
     keys match: the masked-LM backbone, or a fine-tuning checkpoint with its score."""
     from dna_amd.decoders import SequenceClassifier
-    sd = {(k[len("model."):] if k.startswith("model.") else k): v for k, v in state_dict.items()}
+    from dna_amd.trainer import strip_model_prefix
+    sd = strip_model_prefix(state_dict)
     if isinstance(model, SequenceClassifier):
         if any(k.startswith("decoder.0.") for k in sd):
             model.load_state_dict(sd)

@@ -99,11 +99,8 @@ def build_model(cfg, precision):
 
 
 def load_lightning_state(model, path, strict):
-    ck = torch.load(path, map_location="cpu", weights_only=True)
-    sd = ck.get("state_dict", ck)
-    sd = {k[len("model."):] if k.startswith("model.") else k: v for k, v in sd.items()}
-    missing, unexpected = model.load_state_dict(sd, strict=strict)
-    return missing, unexpected
+    from dna_amd.trainer import load_backbone
+    return load_backbone(model, path, strict=strict)
 
 
 def _progress(n):
