@@ -129,6 +129,12 @@ _SIGS = {
     "dna_pool_head_bwd_workspace": (_sz, [_i, _i, _i]),
     "dna_pool_head_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _i64, _vp,
                                _i64, _i, _vp, _vp, _i, _vp, _sz, _vp]),
+    "dna_pool_head_wide_fwd_workspace": (_sz, [_i, _i, _i, _i]),
+    "dna_pool_head_wide_fwd": (_i, [_vp, _i64, _vp, _i64, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i,
+                                    _vp, _vp, _vp, _i, _vp, _vp, _vp, _sz, _vp]),
+    "dna_pool_head_wide_bwd_workspace": (_sz, [_i, _i, _i, _i]),
+    "dna_pool_head_wide_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _i64,
+                                    _vp, _i64, _i, _vp, _vp, _i, _vp, _sz, _vp]),
     "dna_lm_head_fwd_workspace": (_sz, [_i]),
     "dna_lm_head_fwd": (_i, [_vp, _i64, _i, _vp, _i, _vp, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp,
                              _sz, _vp]),

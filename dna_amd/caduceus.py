@@ -25,6 +25,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import functional as DF
+from .decoders import scale_loss
 from .hyena_lm import _LN_COLS, LayerNorm
 from .hyena import HipLinear, hip_linear
 from .mamba import BiMambaWrapper
@@ -414,7 +415,7 @@ class CaduceusForSequenceClassification(nn.Module):
     outputs. pooling_strategy mean | first | last; max is not built."""
 
     def __init__(self, pooling_strategy="mean", conjoin_train=False, conjoin_eval=False,
-                 num_labels=2, problem_type=None, **config):
+                 num_labels=2, problem_type=None, loss_scale=1.0, **config):
         super().__init__()
         if pooling_strategy == "max":
             raise NotImplementedError("CaduceusForSequenceClassification pooling_strategy='max' is "
@@ -427,6 +428,7 @@ class CaduceusForSequenceClassification(nn.Module):
         self.conjoin_train, self.conjoin_eval = conjoin_train, conjoin_eval
         self.num_labels = int(num_labels)
         self.problem_type = problem_type
+        self.loss_scale = float(loss_scale)
         self.caduceus = Caduceus(cfg)
         self.score = nn.Linear(cfg["d_model"], self.num_labels, bias=False)
         ic = cfg["initializer_cfg"] or {}
@@ -456,7 +458,12 @@ class CaduceusForSequenceClassification(nn.Module):
         return self.problem_type
 
     def cls_logits(self, input_ids, labels=None):
-        """-> (logits [B, num_labels] fp32, loss | None, pred | None)."""
+        """-> (logits [B, num_labels] fp32, loss | None, pred | None); the loss is the head's
+        times loss_scale (tasks.pool_loss: customMSE's sum over the columns)."""
+        logits, loss, pred = self._head(input_ids, labels)
+        return logits, scale_loss(loss, self.loss_scale), pred
+
+    def _head(self, input_ids, labels=None):
         kw = {}
         if labels is not None:
             kw = dict(labels=labels, problem_type=self._problem(labels))

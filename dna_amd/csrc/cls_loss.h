@@ -7,6 +7,23 @@
 
 namespace dna {
 
+// One element of the regression (MSE) or multi-label (BCE with logits) loss in arithmetic T: its
+// term is added to acc, its dlogits (times inv_n) comes back. cls_loss below walks a row with it;
+// the wide pooling head (pool_head.hip) spreads the B x C elements over a grid.
+template <typename T>
+__device__ __forceinline__ float cls_loss_elem(int problem, T v, T yc, T inv_nt, double& acc) {
+  if (problem == DNA_CLS_REGRESSION) {
+    const T d = v - yc;
+    acc += (double)d * (double)d;
+    return (float)((T)2 * d * inv_nt);
+  }
+  // BCE with logits: max(v, 0) - v y + log1p(exp(-|v|))
+  const T e = exp(-fabs(v));
+  acc += (double)(fmax(v, (T)0) - v * yc + log1p(e));
+  const T sig = v >= (T)0 ? (T)1 / ((T)1 + e) : e / ((T)1 + e);
+  return (float)((sig - yc) * inv_nt);
+}
+
 // For one workgroup of 1024 threads: loss, dlogits and (single-label) pred of logits [B, C], a
 // thread per row (b = tid, tid + 1024, ...). T is the arithmetic type of a row. float: what the
 // DNABERT-2 head computes. double: a batch of a few rows leaves dlogits of magnitude 1 / B whose
@@ -46,19 +63,7 @@ __device__ __forceinline__ void cls_loss(const float* logits, const void* labels
       if (pred) pred[b] = arg;
     } else {
       const float* y = reinterpret_cast<const float*>(labels) + (size_t)b * C;
-      for (int c = 0; c < C; ++c) {
-        const T v = lg[c], yc = y[c];
-        if (problem == DNA_CLS_REGRESSION) {
-          const T d = v - yc;
-          acc += (double)d * (double)d;
-          dl[c] = (float)((T)2 * d * inv_nt);
-        } else {  // BCE with logits: max(v, 0) - v y + log1p(exp(-|v|))
-          const T e = exp(-fabs(v));
-          acc += (double)(fmax(v, (T)0) - v * yc + log1p(e));
-          const T sig = v >= (T)0 ? (T)1 / ((T)1 + e) : e / ((T)1 + e);
-          dl[c] = (float)((sig - yc) * inv_nt);
-        }
-      }
+      for (int c = 0; c < C; ++c) dl[c] = cls_loss_elem<T>(problem, lg[c], y[c], inv_nt, acc);
     }
   }
   red[tid] = acc;

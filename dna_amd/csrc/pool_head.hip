@@ -22,6 +22,10 @@
 // writes pooled and computes the logits; loss_kernel is dna_cls_loss's losses with the row
 // arithmetic in double (one workgroup).
 // Backward: grad_kernel (g, dW, dbias), then bcast_kernel writes every element of dx once.
+//
+// These kernels take up to 64 labels. The wide head (dna_pool_head_wide_*: up to 1024 labels,
+// regression and multi-label) shares partial_kernel and bcast_kernel and has its own stages in
+// between; see "the wide head" below.
 #include <type_traits>
 
 #include "cls_loss.h"
@@ -206,14 +210,12 @@ struct FinArgs {
   float* pooled; float* logits;
 };
 
-// One workgroup per sequence, 1024 threads = cw columns (of four channels) x 1024 / cw chunk
-// groups. A thread adds its group's chunks in index order (16-B loads, eight in flight), then the
-// groups are added in index order through LDS. Behind a workgroup barrier a wave per class takes
-// the dot product with W (lanes stride over D, fixed shuffle tree).
-__global__ __launch_bounds__(1024) void finish_kernel(FinArgs g) {
-  __shared__ float4 red[1024];
-  const int tid = threadIdx.x, b = blockIdx.x, lane = tid & 63;
-  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+// The pooled row of sequence b from its chunks, by a workgroup of 1024 threads = cw columns (of
+// four channels) x 1024 / cw chunk groups. A thread adds its group's chunks in index order (16-B
+// loads, eight in flight), then the groups are added in index order through LDS. Ends behind a
+// workgroup barrier: every thread may read the row of pooled it wrote.
+__device__ __forceinline__ void pooled_row(const FinArgs& g, int b, float4 (&red)[1024]) {
+  const int tid = threadIdx.x;
   const int cw = 1 << g.cw_log2, ngroups = 1024 >> g.cw_log2;
   const int col = tid & (cw - 1), grp = tid >> g.cw_log2;
   const int n4 = g.Dp >> 2;
@@ -246,8 +248,17 @@ __global__ __launch_bounds__(1024) void finish_kernel(FinArgs g) {
       for (int k = 0; k < 4; ++k)  // the pad channels D .. Dp - 1 hold nothing
         if (c4 * 4 + k < g.D) g.pooled[(int64_t)b * g.D + c4 * 4 + k] = cnt > 0 ? tv[k] / denom : 0.f;
     }
-    __syncthreads();  // red is reused; pooled is read below by other threads of this workgroup
+    __syncthreads();  // red is reused; pooled is read by other threads of this workgroup
   }
+}
+
+// One workgroup per sequence: its pooled row, then a wave per class takes the dot product with W
+// (lanes stride over D, fixed shuffle tree).
+__global__ __launch_bounds__(1024) void finish_kernel(FinArgs g) {
+  __shared__ float4 red[1024];
+  const int tid = threadIdx.x, b = blockIdx.x, lane = tid & 63;
+  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+  pooled_row(g, b, red);
   const float* pb = g.pooled + (int64_t)b * g.D;
   for (int c = w; c < g.C; c += 16) {
     const float* wr = g.W + (int64_t)c * g.D;
@@ -360,6 +371,208 @@ __global__ __launch_bounds__(TPB) void bcast_kernel(BcastArgs g) {
   }
 }
 
+// ------------------------------------------------------------------- the wide head (C <= 1024)
+// finish_kernel reads all of W once per sequence, loss_kernel is one workgroup with a thread per
+// row, grad_kernel's dbias workgroup has a thread per class: none of them scales in C. The wide
+// head keeps partial_kernel and bcast_kernel and replaces the stages between them: pooled_kernel
+// (pooled_row alone), three small products on one 32 x 32 tile routine (logits, gs, dW) that read
+// each operand once per 32 rows of the other, 128 reduction indices per step, the loss spread over the grid, dbias by column
+// slices. The products accumulate in double in index order, so each output carries one rounding.
+
+__global__ __launch_bounds__(1024) void pooled_kernel(FinArgs g) {
+  __shared__ float4 red[1024];
+  pooled_row(g, blockIdx.x, red);
+}
+
+constexpr int TILE = 32;   // rows and columns of a workgroup's tile (256 threads)
+constexpr int KSTEP = 128;  // reduction indices staged per step: 16 + 16 loads in flight per thread
+
+struct TileLds {
+  float a[KSTEP][TILE + 1], b[KSTEP][TILE + 1];
+};
+
+// one operand's [KSTEP][TILE] tile: element (r, k) of the tile is P[(r0 + r) * ld + k0 + k], or
+// P[(k0 + k) * ld + r0 + r] when T
+template <bool T>
+__device__ __forceinline__ void stage_tile(const float* P, int64_t ld, int R, int K, int r0, int k0,
+                                           float (&s)[KSTEP][TILE + 1]) {
+  const int tid = threadIdx.x;
+  constexpr int PER = KSTEP * TILE / 256;
+  float v[PER];
+  // every load is issued, at a clamped index, before the first value is used: a load under its
+  // bounds test waits for the one before it
+#pragma unroll
+  for (int u = 0; u < PER; ++u) {
+    const int r = T ? (tid & (TILE - 1)) : (tid >> 7) + 2 * u;
+    const int k = T ? (tid >> 5) + 8 * u : (tid & (KSTEP - 1));
+    const bool ok = r0 + r < R && k0 + k < K;
+    const int64_t at = T ? (int64_t)(k0 + k) * ld + r0 + r : (int64_t)(r0 + r) * ld + k0 + k;
+    v[u] = P[ok ? at : 0];
+  }
+#pragma unroll
+  for (int u = 0; u < PER; ++u) {
+    const int r = T ? (tid & (TILE - 1)) : (tid >> 7) + 2 * u;
+    const int k = T ? (tid >> 5) + 8 * u : (tid & (KSTEP - 1));
+    s[k][r] = (r0 + r < R && k0 + k < K) ? v[u] : 0.f;
+  }
+}
+
+// acc[i][j] = sum_k a(m0 + 2 ty + i, k) b(k, n0 + 2 tx + j) over k = 0 .. K - 1 in index order,
+// for the 256 threads (tx = tid % 16, ty = tid / 16) of a workgroup. a(m, k) is A[m * lda + k],
+// or A[k * lda + m] when AT; b(k, n) is Bm[n * ldb + k], or Bm[k * ldb + n] when BT. Rows past
+// M, columns past N and steps past K read nothing and count as zero. Tiles are staged through
+// LDS as [k][m] and [k][n], loaded along the operand's contiguous index.
+template <bool AT, bool BT>
+__device__ __forceinline__ void tile_product(const float* A, int64_t lda, const float* Bm,
+                                             int64_t ldb, int M, int N, int K, int m0, int n0,
+                                             TileLds& lds, double (&acc)[2][2]) {
+  const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
+  acc[0][0] = acc[0][1] = acc[1][0] = acc[1][1] = 0.0;
+  for (int k0 = 0; k0 < K; k0 += KSTEP) {
+    stage_tile<AT>(A, lda, M, K, m0, k0, lds.a);
+    stage_tile<BT>(Bm, ldb, N, K, n0, k0, lds.b);
+    __syncthreads();
+#pragma unroll 8
+    for (int k = 0; k < KSTEP; ++k) {
+      const double a0 = lds.a[k][2 * ty], a1 = lds.a[k][2 * ty + 1];
+      const double b0 = lds.b[k][2 * tx], b1 = lds.b[k][2 * tx + 1];
+      acc[0][0] = fma(a0, b0, acc[0][0]);
+      acc[0][1] = fma(a0, b1, acc[0][1]);
+      acc[1][0] = fma(a1, b0, acc[1][0]);
+      acc[1][1] = fma(a1, b1, acc[1][1]);
+    }
+    __syncthreads();
+  }
+}
+
+// logits = pooled W^T (+ bias): grid (C tiles, B tiles)
+__global__ __launch_bounds__(256) void wide_logits_kernel(const float* pooled, const float* W,
+                                                          const float* bias, int B, int D, int C,
+                                                          float* logits) {
+  __shared__ TileLds lds;
+  const int m0 = blockIdx.y * TILE, n0 = blockIdx.x * TILE;
+  double acc[2][2];
+  tile_product<false, false>(pooled, D, W, D, B, C, D, m0, n0, lds, acc);
+  const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      const int b = m0 + 2 * ty + i, c = n0 + 2 * tx + j;
+      if (b < B && c < C)
+        logits[(int64_t)b * C + c] = (float)(acc[i][j] + (bias ? (double)bias[c] : 0.0));
+    }
+}
+
+constexpr int LOSS_TPB = 256, LOSS_PER = 2;  // a loss workgroup takes 512 consecutive elements
+
+static int64_t wide_loss_blocks(int B, int C) {
+  return ((int64_t)B * C + LOSS_TPB * LOSS_PER - 1) / (LOSS_TPB * LOSS_PER);
+}
+
+// cls_loss.h's regression / multi-label element over the B x C elements, an element per thread
+// and step, in double; the workgroup's terms are added by a fixed tree into part[blockIdx.x]
+__global__ __launch_bounds__(LOSS_TPB) void wide_loss_kernel(const float* logits,
+                                                             const float* labels, int problem,
+                                                             int64_t n, float* dlogits,
+                                                             double* part) {
+  __shared__ double red[LOSS_TPB];
+  const int tid = threadIdx.x;
+  const double inv_n = 1.0 / (double)n;
+  double acc = 0.0;
+#pragma unroll
+  for (int u = 0; u < LOSS_PER; ++u) {
+    const int64_t i = ((int64_t)blockIdx.x * LOSS_PER + u) * LOSS_TPB + tid;
+    if (i < n)
+      dlogits[i] = cls_loss_elem<double>(problem, (double)logits[i], (double)labels[i], inv_n, acc);
+  }
+  red[tid] = acc;
+  __syncthreads();
+  for (int s = LOSS_TPB / 2; s > 0; s >>= 1) {
+    if (tid < s) red[tid] += red[tid + s];
+    __syncthreads();
+  }
+  if (tid == 0) part[blockIdx.x] = red[0];
+}
+
+// loss = (the workgroups' sums, each thread its strided share in index order, then a fixed
+// tree) / n; one workgroup
+__global__ __launch_bounds__(1024) void wide_loss_finish_kernel(const double* part, int64_t nparts,
+                                                                int64_t n, float* loss) {
+  __shared__ double red[1024];
+  const int tid = threadIdx.x;
+  double acc = 0.0;
+  for (int64_t i = tid; i < nparts; i += 1024) acc += part[i];
+  red[tid] = acc;
+  __syncthreads();
+  for (int s = 512; s > 0; s >>= 1) {
+    if (tid < s) red[tid] += red[tid + s];
+    __syncthreads();
+  }
+  if (tid == 0) loss[0] = (float)(red[0] / (double)n);
+}
+
+// One launch, three kinds of workgroup, as grad_kernel: gs tiles (dlogits W, K = C), dW tiles
+// (dlogits^T pooled, K = B), dbias (32 classes x 8 row slices per workgroup: a slice adds its
+// rows b = slice, slice + 8, ... in double, the slices are added in slice order).
+__global__ __launch_bounds__(256) void wide_grad_kernel(GradArgs g) {
+  __shared__ TileLds lds;
+  const double up = g.upstream ? (double)g.upstream[0] : 1.0;
+  const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
+  const int dtiles = (g.D + TILE - 1) / TILE;
+  int bid = blockIdx.x;
+  double acc[2][2];
+  if (bid < g.blocks_g) {
+    const int m0 = (bid / dtiles) * TILE, n0 = (bid % dtiles) * TILE;
+    tile_product<false, true>(g.dl, g.C, g.W, g.D, g.B, g.D, g.C, m0, n0, lds, acc);
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const int b = m0 + 2 * ty + i;
+      if (b >= g.B) continue;
+      int st, cnt;
+      window(g.start, g.count, b, g.L, st, cnt);
+      const double denom = (double)cnt * (g.two ? 2.0 : 1.0);
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+        const int d = n0 + 2 * tx + j;
+        if (d < g.D) g.gs[(int64_t)b * g.Dp + d] = cnt > 0 ? (float)(acc[i][j] * up / denom) : 0.f;
+      }
+    }
+    return;
+  }
+  bid -= g.blocks_g;
+  if (bid < g.blocks_w) {
+    const int m0 = (bid / dtiles) * TILE, n0 = (bid % dtiles) * TILE;
+    tile_product<true, true>(g.dl, g.C, g.pooled, g.D, g.C, g.D, g.B, m0, n0, lds, acc);
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+        const int c = m0 + 2 * ty + i, d = n0 + 2 * tx + j;
+        if (c >= g.C || d >= g.D) continue;
+        const int64_t idx = (int64_t)c * g.D + d;
+        const float sv = (float)(acc[i][j] * up);
+        g.dW[idx] = g.accumulate ? g.dW[idx] + sv : sv;
+      }
+    return;
+  }
+  bid -= g.blocks_w;
+  if (!g.dbias) return;
+  __shared__ double col[8][TILE];
+  const int cl = tid & (TILE - 1), slice = tid >> 5;
+  const int c = bid * TILE + cl;
+  double s = 0.0;  // a sum of B values that mostly cancel
+  if (c < g.C)
+    for (int b = slice; b < g.B; b += 8) s += (double)g.dl[(int64_t)b * g.C + c];
+  col[slice][cl] = s;
+  __syncthreads();
+  if (slice == 0 && c < g.C) {
+    for (int u = 1; u < 8; ++u) s += col[u][cl];
+    const float sv = (float)(s * up);
+    g.dbias[c] = g.accumulate ? g.dbias[c] + sv : sv;
+  }
+}
+
 // 16-byte accesses when D, the strides and the base pointers allow them, else one element
 static int pick_vec(int dtype, int D, const void* p1, int64_t s1, const void* p2, int64_t s2) {
   const int v = dtype == DNA_BF16 ? 8 : 4;
@@ -368,11 +581,11 @@ static int pick_vec(int dtype, int D, const void* p1, int64_t s1, const void* p2
   return ok ? v : 1;
 }
 
-static int shape_check(const char* name, int B, int L, int D, int C, int dtype) {
+static int shape_check(const char* name, int B, int L, int D, int C, int dtype, int cmax = 64) {
   DNA_CHECK_ARG(B >= 1 && B <= 65535, "%s: batch must be in [1, 65535] (got %d)", name, B);
   DNA_CHECK_ARG(L >= 1, "%s: length must be >= 1 (got %d)", name, L);
   DNA_CHECK_ARG(D >= 1, "%s: width must be >= 1 (got %d)", name, D);
-  DNA_CHECK_ARG(C >= 1 && C <= 64, "%s: 1 <= labels <= 64 required (got %d)", name, C);
+  DNA_CHECK_ARG(C >= 1 && C <= cmax, "%s: 1 <= labels <= %d required (got %d)", name, cmax, C);
   DNA_CHECK_ARG(dtype == DNA_F32 || dtype == DNA_BF16, "%s: x must be fp32 or bf16", name);
   return DNA_OK;
 }
@@ -382,33 +595,49 @@ static int shape_check(const char* name, int B, int L, int D, int C, int dtype) 
 
 using namespace dna;
 
+// bytes of part[B][nchunks][Dp]; the wide head's loss partial sums (double) follow at a multiple of 16
+static size_t part_bytes(int B, int L, int D) {
+  const size_t n = (size_t)B * pool::pool_nchunks(B, L, D) * pool::pool_dp(D) * sizeof(float);
+  return (n + 15) / 16 * 16;
+}
+
 extern "C" size_t dna_pool_head_fwd_workspace(int B, int L, int D) {
   if (B < 1 || L < 1 || D < 1) return 0;
   return (size_t)B * pool::pool_nchunks(B, L, D) * pool::pool_dp(D) * sizeof(float);
 }
 
-extern "C" int dna_pool_head_fwd(const void* x1, int64_t x1_stride, const void* x2,
-                                 int64_t x2_stride, int flip2, int x_dtype, const int32_t* start,
-                                 const int32_t* count, const float* W, const float* bias, int B,
-                                 int L, int D, int C, float* pooled, float* logits,
-                                 const void* labels, int problem_type, float* loss, float* dlogits,
-                                 int64_t* pred, void* workspace, size_t workspace_bytes,
-                                 void* stream) {
-  int st = pool::shape_check("dna_pool_head_fwd", B, L, D, C, x_dtype);
+extern "C" size_t dna_pool_head_wide_fwd_workspace(int B, int L, int D, int C) {
+  if (B < 1 || L < 1 || D < 1 || C < 1) return 0;
+  return part_bytes(B, L, D) + (size_t)pool::wide_loss_blocks(B, C) * sizeof(double);
+}
+
+// Both forwards: partial_kernel, then the narrow head's finish_kernel + loss_kernel or the wide
+// head's pooled_kernel + wide_logits_kernel + wide_loss_kernel + wide_loss_finish_kernel.
+static int pool_fwd(const char* name, bool wide, const void* x1, int64_t x1_stride, const void* x2,
+                    int64_t x2_stride, int flip2, int x_dtype, const int32_t* start,
+                    const int32_t* count, const float* W, const float* bias, int B, int L, int D,
+                    int C, float* pooled, float* logits, const void* labels, int problem_type,
+                    float* loss, float* dlogits, int64_t* pred, void* workspace,
+                    size_t workspace_bytes, void* stream) {
+  int st = pool::shape_check(name, B, L, D, C, x_dtype, wide ? 1024 : 64);
   if (st != DNA_OK) return st;
-  DNA_CHECK_ARG(x1 && W && pooled && logits, "dna_pool_head_fwd: null pointer");
-  DNA_CHECK_ARG((flip2 & ~3) == 0, "dna_pool_head_fwd: bad flip2 flags %d", flip2);
+  DNA_CHECK_ARG(x1 && W && pooled && logits, "%s: null pointer", name);
+  DNA_CHECK_ARG((flip2 & ~3) == 0, "%s: bad flip2 flags %d", name, flip2);
   if (labels) {
+    DNA_CHECK_ARG(!wide || problem_type != DNA_CLS_SINGLE_LABEL,
+                  "%s: problem type single_label_classification is not built for the wide head "
+                  "(regression and multi_label_classification are)", name);
     DNA_CHECK_ARG(problem_type == DNA_CLS_REGRESSION || problem_type == DNA_CLS_SINGLE_LABEL ||
                       problem_type == DNA_CLS_MULTI_LABEL,
-                  "dna_pool_head_fwd: bad problem type %d", problem_type);
-    DNA_CHECK_ARG(loss && dlogits, "dna_pool_head_fwd: null loss / dlogits");
+                  "%s: bad problem type %d", name, problem_type);
+    DNA_CHECK_ARG(loss && dlogits, "%s: null loss / dlogits", name);
   }
-  DNA_CHECK_ARG(x1_stride >= D && (!x2 || x2_stride >= D),
-                "dna_pool_head_fwd: position strides must be >= D");
-  const size_t need = dna_pool_head_fwd_workspace(B, L, D);
+  DNA_CHECK_ARG(x1_stride >= D && (!x2 || x2_stride >= D), "%s: position strides must be >= D",
+                name);
+  const size_t need = wide ? dna_pool_head_wide_fwd_workspace(B, L, D, C)
+                           : dna_pool_head_fwd_workspace(B, L, D);
   DNA_CHECK_ARG(workspace && workspace_bytes >= need && aligned(workspace, 16),
-                "dna_pool_head_fwd: workspace too small or not 16-byte aligned (%zu < %zu)",
+                "%s: workspace too small or not 16-byte aligned (%zu < %zu)", name,
                 workspace_bytes, need);
   hipStream_t s = as_stream(stream);
   const int vec = pool::pick_vec(x_dtype, D, x1, x1_stride, x2, x2_stride);
@@ -425,19 +654,63 @@ extern "C" int dna_pool_head_fwd(const void* x1, int64_t x1_stride, const void* 
     if (vec > 1) hipLaunchKernelGGL((pool::partial_kernel<false, 4>), grid, dim3(pool::TPB), 0, s, pa);
     else hipLaunchKernelGGL((pool::partial_kernel<false, 1>), grid, dim3(pool::TPB), 0, s, pa);
   }
-  DNA_LAUNCH_CHECK("dna_pool_head_fwd");
+  DNA_LAUNCH_CHECK(name);
   int cw_log2 = 0;
   while ((1 << cw_log2) < Dp / 4 && cw_log2 < 8) ++cw_log2;
   pool::FinArgs fa{(const float*)workspace, pl.nchunks, L, D, Dp, C, cw_log2, x2 != nullptr,
                    start, count, W, bias, pooled, logits};
-  hipLaunchKernelGGL(pool::finish_kernel, dim3((unsigned)B), dim3(1024), 0, s, fa);
-  DNA_LAUNCH_CHECK("dna_pool_head_fwd");
+  if (!wide) {
+    hipLaunchKernelGGL(pool::finish_kernel, dim3((unsigned)B), dim3(1024), 0, s, fa);
+    DNA_LAUNCH_CHECK(name);
+    if (labels) {
+      hipLaunchKernelGGL(pool::loss_kernel, dim3(1), dim3(1024), 0, s, logits, labels,
+                         problem_type, B, C, loss, dlogits, pred);
+      DNA_LAUNCH_CHECK(name);
+    }
+    return DNA_OK;
+  }
+  hipLaunchKernelGGL(pool::pooled_kernel, dim3((unsigned)B), dim3(1024), 0, s, fa);
+  DNA_LAUNCH_CHECK(name);
+  const dim3 lgrid((unsigned)((C + pool::TILE - 1) / pool::TILE),
+                   (unsigned)((B + pool::TILE - 1) / pool::TILE));
+  hipLaunchKernelGGL(pool::wide_logits_kernel, lgrid, dim3(256), 0, s, (const float*)pooled, W,
+                     bias, B, D, C, logits);
+  DNA_LAUNCH_CHECK(name);
   if (labels) {
-    hipLaunchKernelGGL(pool::loss_kernel, dim3(1), dim3(1024), 0, s, logits, labels, problem_type,
-                       B, C, loss, dlogits, pred);
-    DNA_LAUNCH_CHECK("dna_pool_head_fwd");
+    const int64_t n = (int64_t)B * C, nparts = pool::wide_loss_blocks(B, C);
+    double* lpart = reinterpret_cast<double*>((char*)workspace + part_bytes(B, L, D));
+    hipLaunchKernelGGL(pool::wide_loss_kernel, dim3((unsigned)nparts), dim3(pool::LOSS_TPB), 0, s,
+                       (const float*)logits, (const float*)labels, problem_type, n, dlogits, lpart);
+    DNA_LAUNCH_CHECK(name);
+    hipLaunchKernelGGL(pool::wide_loss_finish_kernel, dim3(1), dim3(1024), 0, s,
+                       (const double*)lpart, nparts, n, loss);
+    DNA_LAUNCH_CHECK(name);
   }
   return DNA_OK;
+}
+
+extern "C" int dna_pool_head_fwd(const void* x1, int64_t x1_stride, const void* x2,
+                                 int64_t x2_stride, int flip2, int x_dtype, const int32_t* start,
+                                 const int32_t* count, const float* W, const float* bias, int B,
+                                 int L, int D, int C, float* pooled, float* logits,
+                                 const void* labels, int problem_type, float* loss, float* dlogits,
+                                 int64_t* pred, void* workspace, size_t workspace_bytes,
+                                 void* stream) {
+  return pool_fwd("dna_pool_head_fwd", false, x1, x1_stride, x2, x2_stride, flip2, x_dtype, start,
+                  count, W, bias, B, L, D, C, pooled, logits, labels, problem_type, loss, dlogits,
+                  pred, workspace, workspace_bytes, stream);
+}
+
+extern "C" int dna_pool_head_wide_fwd(const void* x1, int64_t x1_stride, const void* x2,
+                                      int64_t x2_stride, int flip2, int x_dtype,
+                                      const int32_t* start, const int32_t* count, const float* W,
+                                      const float* bias, int B, int L, int D, int C, float* pooled,
+                                      float* logits, const void* labels, int problem_type,
+                                      float* loss, float* dlogits, void* workspace,
+                                      size_t workspace_bytes, void* stream) {
+  return pool_fwd("dna_pool_head_wide_fwd", true, x1, x1_stride, x2, x2_stride, flip2, x_dtype,
+                  start, count, W, bias, B, L, D, C, pooled, logits, labels, problem_type, loss,
+                  dlogits, nullptr, workspace, workspace_bytes, stream);
 }
 
 extern "C" size_t dna_pool_head_bwd_workspace(int B, int L, int D) {
@@ -446,31 +719,45 @@ extern "C" size_t dna_pool_head_bwd_workspace(int B, int L, int D) {
   return (size_t)B * pool::pool_dp(D) * sizeof(float);
 }
 
-extern "C" int dna_pool_head_bwd(const float* dlogits, const float* upstream, const float* pooled,
-                                 const float* W, const int32_t* start, const int32_t* count, int B,
-                                 int L, int D, int C, int x_dtype, void* dx1, int64_t dx1_stride,
-                                 void* dx2, int64_t dx2_stride, int flip2, float* dW, float* dbias,
-                                 int accumulate, void* workspace, size_t workspace_bytes,
-                                 void* stream) {
-  int st = pool::shape_check("dna_pool_head_bwd", B, L, D, C, x_dtype);
+extern "C" size_t dna_pool_head_wide_bwd_workspace(int B, int L, int D, int C) {
+  return C < 1 ? 0 : dna_pool_head_bwd_workspace(B, L, D);
+}
+
+// Both backwards: grad_kernel or wide_grad_kernel (gs, dW, dbias), then bcast_kernel.
+static int pool_bwd(const char* name, bool wide, const float* dlogits, const float* upstream,
+                    const float* pooled, const float* W, const int32_t* start,
+                    const int32_t* count, int B, int L, int D, int C, int x_dtype, void* dx1,
+                    int64_t dx1_stride, void* dx2, int64_t dx2_stride, int flip2, float* dW,
+                    float* dbias, int accumulate, void* workspace, size_t workspace_bytes,
+                    void* stream) {
+  int st = pool::shape_check(name, B, L, D, C, x_dtype, wide ? 1024 : 64);
   if (st != DNA_OK) return st;
-  DNA_CHECK_ARG(dlogits && pooled && W && dW, "dna_pool_head_bwd: null pointer");
-  DNA_CHECK_ARG(dx1 || !dx2, "dna_pool_head_bwd: dx2 without dx1");
-  DNA_CHECK_ARG((flip2 & ~3) == 0, "dna_pool_head_bwd: bad flip2 flags %d", flip2);
+  DNA_CHECK_ARG(dlogits && pooled && W && dW, "%s: null pointer", name);
+  DNA_CHECK_ARG(dx1 || !dx2, "%s: dx2 without dx1", name);
+  DNA_CHECK_ARG((flip2 & ~3) == 0, "%s: bad flip2 flags %d", name, flip2);
   DNA_CHECK_ARG((!dx1 || dx1_stride >= D) && (!dx2 || dx2_stride >= D),
-                "dna_pool_head_bwd: position strides must be >= D");
+                "%s: position strides must be >= D", name);
   const size_t need = dna_pool_head_bwd_workspace(B, L, D);
-  DNA_CHECK_ARG(workspace && workspace_bytes >= need,
-                "dna_pool_head_bwd: workspace too small (%zu < %zu)", workspace_bytes, need);
+  DNA_CHECK_ARG(workspace && workspace_bytes >= need, "%s: workspace too small (%zu < %zu)", name,
+                workspace_bytes, need);
   hipStream_t s = as_stream(stream);
   const int Dp = pool::pool_dp(D);
   pool::GradArgs ga{dlogits, upstream, pooled, W, start, count, B, L, D, Dp, C, dx2 != nullptr,
                     (float*)workspace, dW, dbias, accumulate ? 1 : 0, 0, 0};
-  ga.blocks_g = (int)(((int64_t)B * D + 255) / 256);
-  ga.blocks_w = (int)(((int64_t)C * D + 255) / 256);
-  hipLaunchKernelGGL(pool::grad_kernel, dim3((unsigned)(ga.blocks_g + ga.blocks_w + 1)), dim3(256),
-                     0, s, ga);
-  DNA_LAUNCH_CHECK("dna_pool_head_bwd");
+  if (wide) {
+    const int64_t dt = (D + pool::TILE - 1) / pool::TILE, ct = (C + pool::TILE - 1) / pool::TILE;
+    const int64_t bg = (B + pool::TILE - 1) / pool::TILE * dt, bw = ct * dt;
+    DNA_CHECK_ARG(bg + bw + ct <= INT32_MAX, "%s: width %d makes too many tiles", name, D);
+    ga.blocks_g = (int)bg;
+    ga.blocks_w = (int)bw;
+    hipLaunchKernelGGL(pool::wide_grad_kernel, dim3((unsigned)(bg + bw + ct)), dim3(256), 0, s, ga);
+  } else {
+    ga.blocks_g = (int)(((int64_t)B * D + 255) / 256);
+    ga.blocks_w = (int)(((int64_t)C * D + 255) / 256);
+    hipLaunchKernelGGL(pool::grad_kernel, dim3((unsigned)(ga.blocks_g + ga.blocks_w + 1)),
+                       dim3(256), 0, s, ga);
+  }
+  DNA_LAUNCH_CHECK(name);
   if (!dx1) return DNA_OK;  // a frozen backbone: nobody reads dx
   const int vec = pool::pick_vec(x_dtype, D, dx1, dx1_stride, dx2, dx2_stride);
   const pool::Plan pl = pool::make_plan(B, L, D, vec);
@@ -485,6 +772,29 @@ extern "C" int dna_pool_head_bwd(const float* dlogits, const float* upstream, co
     if (vec > 1) hipLaunchKernelGGL((pool::bcast_kernel<false, 4>), grid, dim3(pool::TPB), 0, s, ba);
     else hipLaunchKernelGGL((pool::bcast_kernel<false, 1>), grid, dim3(pool::TPB), 0, s, ba);
   }
-  DNA_LAUNCH_CHECK("dna_pool_head_bwd");
+  DNA_LAUNCH_CHECK(name);
   return DNA_OK;
+}
+
+extern "C" int dna_pool_head_bwd(const float* dlogits, const float* upstream, const float* pooled,
+                                 const float* W, const int32_t* start, const int32_t* count, int B,
+                                 int L, int D, int C, int x_dtype, void* dx1, int64_t dx1_stride,
+                                 void* dx2, int64_t dx2_stride, int flip2, float* dW, float* dbias,
+                                 int accumulate, void* workspace, size_t workspace_bytes,
+                                 void* stream) {
+  return pool_bwd("dna_pool_head_bwd", false, dlogits, upstream, pooled, W, start, count, B, L, D,
+                  C, x_dtype, dx1, dx1_stride, dx2, dx2_stride, flip2, dW, dbias, accumulate,
+                  workspace, workspace_bytes, stream);
+}
+
+extern "C" int dna_pool_head_wide_bwd(const float* dlogits, const float* upstream,
+                                      const float* pooled, const float* W, const int32_t* start,
+                                      const int32_t* count, int B, int L, int D, int C,
+                                      int x_dtype, void* dx1, int64_t dx1_stride, void* dx2,
+                                      int64_t dx2_stride, int flip2, float* dW, float* dbias,
+                                      int accumulate, void* workspace, size_t workspace_bytes,
+                                      void* stream) {
+  return pool_bwd("dna_pool_head_wide_bwd", true, dlogits, upstream, pooled, W, start, count, B, L,
+                  D, C, x_dtype, dx1, dx1_stride, dx2, dx2_stride, flip2, dW, dbias, accumulate,
+                  workspace, workspace_bytes, stream);
 }

@@ -73,25 +73,35 @@ class SequenceDecoder(nn.Module):
         return self.head(x, mask=mask, lengths=lengths)[0]
 
 
+def scale_loss(loss, scale):
+    """The head's loss (a mean over B x C) times the task's scale (tasks.pool_loss; customMSE:
+    C). Scaled here, so the head's backward receives the scale as its upstream gradient."""
+    return loss if loss is None or scale == 1.0 else loss * scale
+
+
 class SequenceClassifier(nn.Module):
     """An embedding model (forward(input_ids) -> (hidden_states, None), attribute d_output) and a
     SequenceDecoder on it: what the reference's SequenceLightningModule chains for a
     classification task, under its attribute names `model` and `decoder` (the decoder sits in a
-    one-entry list there, hence the state-dict keys decoder.0.output_transform.*)."""
+    one-entry list there, hence the state-dict keys decoder.0.output_transform.*). problem_type and
+    loss_scale: the task's loss as tasks.pool_loss names it; labels are int64 [B] for
+    single-label and fp32 [B, d_output] otherwise."""
 
     def __init__(self, model, d_output, mode="pool", use_lengths=False,
-                 problem_type="single_label_classification"):
+                 problem_type="single_label_classification", loss_scale=1.0):
         super().__init__()
         self.model = model
         self.decoder = nn.ModuleList([SequenceDecoder(model.d_output, d_output, l_output=0,
                                                       use_lengths=use_lengths, mode=mode)])
         self.num_labels = d_output
         self.problem_type = problem_type
+        self.loss_scale = float(loss_scale)
 
     def cls_logits(self, input_ids, labels=None, mask=None, lengths=None):
         hidden, _ = self.model(input_ids)
-        return self.decoder[0].head(hidden, mask=mask, lengths=lengths, labels=labels,
-                                    problem_type=self.problem_type)
+        logits, loss, pred = self.decoder[0].head(hidden, mask=mask, lengths=lengths,
+                                                  labels=labels, problem_type=self.problem_type)
+        return logits, scale_loss(loss, self.loss_scale), pred
 
     def forward(self, input_ids, labels=None, mask=None, lengths=None):
         logits, loss, _ = self.cls_logits(input_ids, labels, mask, lengths)

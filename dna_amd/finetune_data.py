@@ -2,8 +2,10 @@
 `train.csv` / `dev.csv` / `test.csv`, each row `sequence,label`), tokenised with the C++ BPE
 tokenizer as [CLS] ... [SEP], truncated to max_length, padded per batch; and Genomic Benchmarks
 folders (`<dest>/<name>/<split>/<class>/*.txt`, one sequence per file), tokenised per character
-to a fixed length for the HyenaDNA / Caduceus classifiers."""
+to a fixed length for the HyenaDNA / Caduceus classifiers; and, tokenised the same way, the
+DeepSTARR files (two regression targets per sequence) and the DeepSEA tables (919 0/1 labels)."""
 import csv
+import gzip
 import os
 import random
 
@@ -87,7 +89,43 @@ def string_reverse_complement(seq):
     return seq[::-1].translate(_COMPLEMENT)
 
 
-class GenomicBenchmarkFolder(torch.utils.data.Dataset):
+class _CharItems(torch.utils.data.Dataset):
+    """What the character-level fine-tuning datasets share: how a sequence becomes an item.
+    Tokenisation as the reference calls its tokenizer: truncation to max_length, padding to
+    max_length on the tokenizer's side (left by default), add_eos appends [SEP] inside max_length,
+    rc_aug replaces a sequence by its reverse complement with probability 1/2 per access (`rng`:
+    a random.Random, for seeded draws). Items are (ids int64 [max_length], target) and, with
+    return_mask, the attention mask (bool [max_length], False on padding) as a third entry."""
+
+    def _init_items(self, max_length, tokenizer, use_padding, add_eos, rc_aug, return_mask, rng):
+        self.max_length = int(max_length)
+        self.tokenizer = tokenizer or CharacterTokenizer(["A", "C", "G", "T", "N"],
+                                                         self.max_length + 2)
+        self.use_padding, self.add_eos = use_padding, add_eos
+        self.rc_aug, self.return_mask = rc_aug, return_mask
+        self.rng = rng or random.Random()
+
+    @property
+    def pad_token_id(self):
+        return self.tokenizer.pad_token_id
+
+    def _item(self, x, target):
+        if self.rc_aug and self.rng.random() < 0.5:
+            x = string_reverse_complement(x)
+        ids = self.tokenizer(x, add_special_tokens=bool(self.add_eos),
+                             padding="max_length" if self.use_padding else False,
+                             max_length=self.max_length, truncation=True)["input_ids"]
+        ids = torch.tensor(ids, dtype=torch.int64)
+        if self.return_mask:
+            return ids, target, ids != self.pad_token_id
+        return ids, target
+
+    def collate(self, items):
+        """[(ids, target[, mask])] of one fixed length -> stacked tensors, in the same order."""
+        return tuple(torch.stack(col) for col in zip(*items))
+
+
+class GenomicBenchmarkFolder(_CharItems):
     """One split of a Genomic Benchmarks dataset as the reference's GenomicBenchmarkDataset reads
     it (src/dataloaders/datasets/genomic_bench_dataset.py:122-216): the folder
     `<dest_path>/<dataset_name>/<split>/<class>/` holds one text file per sequence; split "val"
@@ -115,12 +153,7 @@ class GenomicBenchmarkFolder(torch.utils.data.Dataset):
             raise FileNotFoundError(
                 f"{self.base_path}: no such folder. Genomic Benchmarks data is not downloaded "
                 f"here; put the dataset at <dest_path>/{dataset_name}/{self.split}/<class>/*.txt")
-        self.max_length = int(max_length)
-        self.tokenizer = tokenizer or CharacterTokenizer(["A", "C", "G", "T", "N"],
-                                                         self.max_length + 2)
-        self.use_padding, self.add_eos = use_padding, add_eos
-        self.rc_aug, self.return_mask = rc_aug, return_mask
-        self.rng = rng or random.Random()
+        self._init_items(max_length, tokenizer, use_padding, add_eos, rc_aug, return_mask, rng)
         self.classes = sorted(d for d in os.listdir(self.base_path)
                               if os.path.isdir(os.path.join(self.base_path, d)))
         if not self.classes:
@@ -141,23 +174,126 @@ class GenomicBenchmarkFolder(torch.utils.data.Dataset):
     def __len__(self):
         return len(self.all_labels)
 
-    @property
-    def pad_token_id(self):
-        return self.tokenizer.pad_token_id
+    def __getitem__(self, idx):
+        return self._item(self.all_seqs[idx], torch.tensor(self.all_labels[idx], dtype=torch.int64))
+
+
+DEEPSTARR_TARGETS = ("Dev_log2_enrichment", "Hk_log2_enrichment")
+_DEEPSTARR_SPLITS = {"train": "Train", "val": "Val", "valid": "Val", "test": "Test"}
+
+
+class DeepSTARRFolder(_CharItems):
+    """One split of the DeepSTARR enhancer-activity data as the reference's DeepSTARRDataset
+    reads it (src/dataloaders/datasets/deepstarr.py:123-225): `<dest_path>/Sequences_<Split>.fa`
+    (Split Train | Val | Test; "val" and "valid" read Val) and
+    `<dest_path>/Sequences_activity_<Split>.txt`, tab-separated with a header, of which the two
+    columns DEEPSTARR_TARGETS are taken by name. The FASTA is read as the reference reads it: one
+    sequence line per header, stopping at the first empty line. Nothing is ever downloaded: a
+    missing file is an error that says where it is expected, and so is a FASTA whose sequence
+    count differs from the table's.
+
+    Items are (ids int64 [max_length], target fp32 [2]) (+ mask); tokenisation, add_eos, rc_aug,
+    return_mask and collate as in _CharItems. use_tokenizer=False (the reference's id remap for
+    its diffusion models) is not built."""
+
+    num_labels = d_output = len(DEEPSTARR_TARGETS)
+
+    def __init__(self, dest_path, split, max_length, tokenizer=None, use_padding=True,
+                 add_eos=False, rc_aug=False, return_mask=False, rng=None, use_tokenizer=True):
+        if not use_tokenizer:
+            raise NotImplementedError("DeepSTARRFolder use_tokenizer=False (the diffusion models' "
+                                      "id remap) is not built")
+        if split.lower() not in _DEEPSTARR_SPLITS:
+            raise ValueError(f"split {split!r}: one of {sorted(_DEEPSTARR_SPLITS)}")
+        name = _DEEPSTARR_SPLITS[split.lower()]
+        self.fasta_path = os.path.join(str(dest_path), f"Sequences_{name}.fa")
+        self.table_path = os.path.join(str(dest_path), f"Sequences_activity_{name}.txt")
+        for path in (self.fasta_path, self.table_path):
+            if not os.path.exists(path):
+                raise FileNotFoundError(
+                    f"{path}: no such file. DeepSTARR data is not downloaded here; put "
+                    f"Sequences_{name}.fa and Sequences_activity_{name}.txt into <dest_path>")
+        self._init_items(max_length, tokenizer, use_padding, add_eos, rc_aug, return_mask, rng)
+        with open(self.table_path, newline="") as f:
+            rows = csv.reader(f, delimiter="\t")
+            header = next(rows, [])
+            missing = [c for c in DEEPSTARR_TARGETS if c not in header]
+            if missing:
+                raise ValueError(f"{self.table_path}: no column {missing} in the header {header}")
+            cols = [header.index(c) for c in DEEPSTARR_TARGETS]
+            targets = [[float(r[c]) for c in cols] for r in rows if r]
+        self.targets = torch.tensor(targets, dtype=torch.float32).reshape(-1, len(cols))
+        self.all_seqs = []
+        with open(self.fasta_path) as f:
+            seen_header = False
+            for line in f:
+                line = line.strip()
+                if not line:
+                    break
+                if line.startswith(">"):
+                    seen_header = True
+                    continue
+                if not seen_header:
+                    raise ValueError(f"{self.fasta_path}: a sequence before the first header")
+                self.all_seqs.append(line)
+        if len(self.all_seqs) != len(self.targets):
+            raise ValueError(f"{self.fasta_path}: {len(self.all_seqs)} sequences, but "
+                             f"{self.table_path} has {len(self.targets)} rows of targets")
+
+    def __len__(self):
+        return len(self.all_seqs)
 
     def __getitem__(self, idx):
-        x = self.all_seqs[idx]
-        if self.rc_aug and self.rng.random() < 0.5:
-            x = string_reverse_complement(x)
-        ids = self.tokenizer(x, add_special_tokens=bool(self.add_eos),
-                             padding="max_length" if self.use_padding else False,
-                             max_length=self.max_length, truncation=True)["input_ids"]
-        ids = torch.tensor(ids, dtype=torch.int64)
-        label = torch.tensor(self.all_labels[idx], dtype=torch.int64)
-        if self.return_mask:
-            return ids, label, ids != self.pad_token_id
-        return ids, label
+        return self._item(self.all_seqs[idx], self.targets[idx])
 
-    def collate(self, items):
-        """[(ids, label[, mask])] of one fixed length -> stacked tensors, in the same order."""
-        return tuple(torch.stack(col) for col in zip(*items))
+
+DEEPSEA_LABELS = 919
+
+
+class DeepSEACsv(_CharItems):
+    """One split of the DeepSEA chromatin-profile data as the reference's DeepSEADataset reads it
+    (src/dataloaders/datasets/deepsea.py:121-199): `<dest_path>/<split>.csv.gz` (train | valid |
+    test; "val" reads valid), no header, column 0 the sequence and columns 1 .. 919 the 0/1
+    labels. Read with gzip + csv; the labels are held as one uint8 array [rows, 919]. max_rows:
+    only the first rows of the file are kept -- the reference hard-codes 40,000 per split, the
+    default here; None reads everything. Nothing is ever downloaded: a missing file is an error
+    that says where it is expected.
+
+    Items are (ids int64 [max_length], target fp32 [919]) (+ mask); tokenisation, add_eos, rc_aug,
+    return_mask and collate as in _CharItems."""
+
+    num_labels = d_output = DEEPSEA_LABELS
+
+    def __init__(self, dest_path, split, max_length, max_rows=40000, tokenizer=None,
+                 use_padding=True, add_eos=False, rc_aug=False, return_mask=False, rng=None,
+                 use_tokenizer=True):
+        if not use_tokenizer:
+            raise NotImplementedError("DeepSEACsv use_tokenizer=False (the diffusion models' id "
+                                      "remap) is not built")
+        split = "valid" if split.lower() == "val" else split.lower()
+        if split not in ("train", "valid", "test"):
+            raise ValueError(f"split {split!r}: one of train, val / valid, test")
+        self.path = os.path.join(str(dest_path), f"{split}.csv.gz")
+        if not os.path.exists(self.path):
+            raise FileNotFoundError(
+                f"{self.path}: no such file. DeepSEA data is not downloaded here; put train.csv.gz, "
+                "valid.csv.gz and test.csv.gz into <dest_path>")
+        self._init_items(max_length, tokenizer, use_padding, add_eos, rc_aug, return_mask, rng)
+        self.all_seqs, rows = [], []
+        with gzip.open(self.path, "rt", newline="") as f:
+            for i, row in enumerate(csv.reader(f)):
+                if max_rows is not None and i >= int(max_rows):
+                    break
+                if len(row) != DEEPSEA_LABELS + 1:
+                    raise ValueError(f"{self.path}: row {i} has {len(row)} columns, not a sequence "
+                                     f"and {DEEPSEA_LABELS} labels")
+                self.all_seqs.append(row[0])
+                rows.append(bytes(int(v) for v in row[1:]))
+        self.labels = torch.frombuffer(bytearray(b"".join(rows)), dtype=torch.uint8).reshape(
+            len(rows), DEEPSEA_LABELS) if rows else torch.zeros(0, DEEPSEA_LABELS, dtype=torch.uint8)
+
+    def __len__(self):
+        return len(self.all_seqs)
+
+    def __getitem__(self, idx):
+        return self._item(self.all_seqs[idx], self.labels[idx].to(torch.float32))

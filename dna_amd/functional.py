@@ -1089,6 +1089,11 @@ def _pool_window(name, t, B):
     return t.contiguous()
 
 
+# The head's kernels by label count: up to POOL_NARROW_LABELS the narrow ones (any problem type),
+# up to POOL_WIDE_LABELS the wide ones (regression, multi-label); C alone decides.
+POOL_NARROW_LABELS, POOL_WIDE_LABELS = 64, 1024
+
+
 class PoolHead(torch.autograd.Function):
     """Windowed mean over L + linear (+ loss) on csrc/pool_head.hip, the head of the HyenaDNA
     SequenceDecoder (pool / first / last) and of CaduceusForSequenceClassification:
@@ -1103,7 +1108,9 @@ class PoolHead(torch.autograd.Function):
     mirror2: the second input's window is [L - start - count, L - start), the same positions of
     its sequence flip. start / count: int32 [B] on the device or None (0 / L - start). w [C, D], bias [C] | None: the
     fp32 master parameters in both precisions. Forward 2 launches + the loss's, backward 2; with
-    FlatParams direct gradients dw / dbias are added straight into the flat buffer."""
+    FlatParams direct gradients dw / dbias are added straight into the flat buffer. C > 64 (to
+    1024; regression and multi-label only) runs the wide kernels: forward 3 launches + 2 for the
+    loss, backward 2; a larger C is a ValueError."""
 
     @staticmethod
     def forward(ctx, x, x2, w, bias, start, count, rcps, flip2, mirror2, labels, problem):
@@ -1129,6 +1136,13 @@ class PoolHead(torch.autograd.Function):
             D, xa, xb, flip2, mirror2 = W, x, None, False, False
         flags = int(bool(flip2)) | (int(bool(mirror2)) << 1)
         C = w.shape[0]
+        if C > POOL_WIDE_LABELS:
+            raise ValueError(f"dna_amd: pool head has {C} labels; at most {POOL_WIDE_LABELS} are "
+                             "built")
+        if C > POOL_NARROW_LABELS and labels is not None and problem == N.CLS_SINGLE_LABEL:
+            raise ValueError(f"dna_amd: a single_label_classification pool head takes at most "
+                             f"{POOL_NARROW_LABELS} labels, got {C} (regression and "
+                             f"multi_label_classification go up to {POOL_WIDE_LABELS})")
         if w.dtype != torch.float32 or not w.is_contiguous() or tuple(w.shape) != (C, D):
             raise TypeError(f"dna_amd: pool head weight must be contiguous fp32 [C, {D}], got "
                             f"{w.dtype} {tuple(w.shape)}")
@@ -1142,14 +1156,21 @@ class PoolHead(torch.autograd.Function):
         pooled = torch.empty(B, D, device=dev, dtype=torch.float32)
         logits = torch.empty(B, C, device=dev, dtype=torch.float32)
         labels, loss, dl, pred = _loss_outputs(labels, problem, logits)
-        nws = N.lib().dna_pool_head_fwd_workspace(B, L, D)
-        ws = torch.empty(max(nws // 4, 4), device=dev, dtype=torch.float32)
         nin = 1 if xb is None else 2
+        head = (xa.data_ptr(), s1, _p(xb), s2, flags, _dt(x), _p(start), _p(count), w.data_ptr(),
+                _p(bias), B, L, D, C, pooled.data_ptr(), logits.data_ptr(), _p(labels), problem,
+                _p(loss), _p(dl))
         with _timed("pool_head_fwd", float(nin) * B * L * D * x.element_size(), kind="byte"):
-            N.call("dna_pool_head_fwd", xa.data_ptr(), s1, _p(xb), s2, flags, _dt(x),
-                   _p(start), _p(count), w.data_ptr(), _p(bias), B, L, D, C, pooled.data_ptr(),
-                   logits.data_ptr(), _p(labels), problem, _p(loss), _p(dl), _p(pred),
-                   ws.data_ptr(), ws.numel() * 4, N.stream_ptr())
+            if C <= POOL_NARROW_LABELS:
+                nws = N.lib().dna_pool_head_fwd_workspace(B, L, D)
+                ws = torch.empty(max(nws // 4, 4), device=dev, dtype=torch.float32)
+                N.call("dna_pool_head_fwd", *head, _p(pred), ws.data_ptr(), ws.numel() * 4,
+                       N.stream_ptr())
+            else:
+                nws = N.lib().dna_pool_head_wide_fwd_workspace(B, L, D, C)
+                ws = torch.empty(max(nws // 4, 4), device=dev, dtype=torch.float32)
+                N.call("dna_pool_head_wide_fwd", *head, ws.data_ptr(), ws.numel() * 4,
+                       N.stream_ptr())
         ctx.save_for_backward(w, pooled, dl, start, count)
         ctx.params = (w, bias)
         ctx.cfg = (tuple(x.shape), x.dtype, D, bool(rcps), xb is not None, flags)
@@ -1188,12 +1209,15 @@ class PoolHead(torch.autograd.Function):
                 da, dbuf = dx, dx2
             else:
                 da = dx
-        nws = N.lib().dna_pool_head_bwd_workspace(B, L, D)
+        wide = C > POOL_NARROW_LABELS
+        nws = (N.lib().dna_pool_head_wide_bwd_workspace(B, L, D, C) if wide
+               else N.lib().dna_pool_head_bwd_workspace(B, L, D))
         ws = torch.empty(max(nws // 4, 4), device=dev, dtype=torch.float32)
         nout = (2 if two else 1) if need_dx else 0
         es = 2 if dtype == torch.bfloat16 else 4
         with _timed("pool_head_bwd", float(nout) * B * L * D * es, kind="byte"):
-            N.call("dna_pool_head_bwd", g.data_ptr(), _p(up), pooled.data_ptr(), w.data_ptr(),
+            N.call("dna_pool_head_wide_bwd" if wide else "dna_pool_head_bwd",
+                   g.data_ptr(), _p(up), pooled.data_ptr(), w.data_ptr(),
                    _p(start), _p(count), B, L, D, C, _DT[dtype], _p(da), W, _p(dbuf), W,
                    flags, dw.data_ptr(), _p(db), int(direct), ws.data_ptr(), ws.numel() * 4,
                    N.stream_ptr())

@@ -21,6 +21,9 @@ asserts (flash_attn_triton.py:849-855) -- instead of letting a kernel read out o
     torch.ops.dna_amd.pool_head_fwd(x1, x2, flip2, mirror2, start, count, w, bias, pooled, logits)
     torch.ops.dna_amd.pool_head_bwd(dlogits, pooled, w, start, count, dx1, dx2, flip2, mirror2, dw,
                                     dbias, accumulate)
+    torch.ops.dna_amd.pool_head_wide_fwd(x1, x2, flip2, mirror2, start, count, w, bias, pooled,
+                                         logits, labels, problem, loss, dlogits)   up to 1024 labels
+    torch.ops.dna_amd.pool_head_wide_bwd(... as pool_head_bwd)
     torch.ops.dna_amd.lm_head_fwd(h, w, labels, denom, loss, count, coef)
     torch.ops.dna_amd.lm_head_bwd(coef, h, w, labels, count, upstream, denom, dh, dw, accumulate)
 and the reference's FlashAttention kernel slot with its own signature (flash_attn_triton.py:
@@ -518,6 +521,72 @@ def pool_head_bwd(dlogits: torch.Tensor, pooled: torch.Tensor, w: torch.Tensor,
            N.stream_ptr())
 
 
+@torch.library.custom_op("dna_amd::pool_head_wide_fwd",
+                         mutates_args=("pooled", "logits", "loss", "dlogits"))
+def pool_head_wide_fwd(x1: torch.Tensor, x2: torch.Tensor | None, flip2: bool, mirror2: bool,
+                       start: torch.Tensor | None, count: torch.Tensor | None, w: torch.Tensor,
+                       bias: torch.Tensor | None, pooled: torch.Tensor, logits: torch.Tensor,
+                       labels: torch.Tensor | None, problem: int, loss: torch.Tensor | None,
+                       dlogits: torch.Tensor | None) -> None:
+    """pool_head_fwd for up to 1024 labels (the wide kernels of csrc/pool_head.hip). labels fp32
+    [B, C] with problem = the dna_cls_problem value of regression or multi-label: loss [1] and
+    dlogits [B, C] are written too; labels None: pooled and logits only."""
+    s1 = _pool_x("x1", x1)
+    B, L, D = x1.shape
+    s2 = 0
+    if x2 is not None:
+        s2 = _pool_x("x2", x2)
+        _check(x2.shape == x1.shape and x2.dtype == x1.dtype, "x2 must match x1")
+    C = w.shape[0]
+    for n, t, shape in (("w", w, (C, D)), ("bias", bias, (C,)), ("pooled", pooled, (B, D)),
+                        ("logits", logits, (B, C)), ("labels", labels, (B, C)), ("loss", loss, (1,)),
+                        ("dlogits", dlogits, (B, C))):
+        if t is None:
+            continue
+        _cuda_contig(n, t, (torch.float32,))
+        _check(tuple(t.shape) == shape, f"{n} must be {shape}, got {tuple(t.shape)}")
+    _check(labels is None or (loss is not None and dlogits is not None),
+           "labels need loss and dlogits")
+    _pool_win("start", start, B)
+    _pool_win("count", count, B)
+    nws = N.lib().dna_pool_head_wide_fwd_workspace(B, L, D, C)
+    ws = torch.empty(max(nws // 4, 4), device=x1.device, dtype=torch.float32)
+    N.call("dna_pool_head_wide_fwd", x1.data_ptr(), s1, _p(x2), s2,
+           int(flip2) | (int(mirror2) << 1), _DT[x1.dtype], _p(start), _p(count), w.data_ptr(),
+           _p(bias), B, L, D, C, pooled.data_ptr(), logits.data_ptr(), _p(labels), int(problem),
+           _p(loss), _p(dlogits), ws.data_ptr(), ws.numel() * 4, N.stream_ptr())
+
+
+@torch.library.custom_op("dna_amd::pool_head_wide_bwd",
+                         mutates_args=("dx1", "dx2", "dw", "dbias"))
+def pool_head_wide_bwd(dlogits: torch.Tensor, pooled: torch.Tensor, w: torch.Tensor,
+                       start: torch.Tensor | None, count: torch.Tensor | None, dx1: torch.Tensor,
+                       dx2: torch.Tensor | None, flip2: bool, mirror2: bool, dw: torch.Tensor,
+                       dbias: torch.Tensor | None, accumulate: bool) -> None:
+    """pool_head_bwd for up to 1024 labels: the same arguments and results."""
+    s1 = _pool_x("dx1", dx1)
+    B, L, D = dx1.shape
+    s2 = 0
+    if dx2 is not None:
+        s2 = _pool_x("dx2", dx2)
+        _check(dx2.shape == dx1.shape and dx2.dtype == dx1.dtype, "dx2 must match dx1")
+    C = w.shape[0]
+    for n, t, shape in (("dlogits", dlogits, (B, C)), ("pooled", pooled, (B, D)), ("w", w, (C, D)),
+                        ("dw", dw, (C, D)), ("dbias", dbias, (C,))):
+        if t is None:
+            continue
+        _cuda_contig(n, t, (torch.float32,))
+        _check(tuple(t.shape) == shape, f"{n} must be {shape}, got {tuple(t.shape)}")
+    _pool_win("start", start, B)
+    _pool_win("count", count, B)
+    nws = N.lib().dna_pool_head_wide_bwd_workspace(B, L, D, C)
+    ws = torch.empty(max(nws // 4, 4), device=dx1.device, dtype=torch.float32)
+    N.call("dna_pool_head_wide_bwd", dlogits.data_ptr(), None, pooled.data_ptr(), w.data_ptr(),
+           _p(start), _p(count), B, L, D, C, _DT[dx1.dtype], dx1.data_ptr(), s1, _p(dx2), s2,
+           int(flip2) | (int(mirror2) << 1), dw.data_ptr(), _p(dbias), int(accumulate),
+           ws.data_ptr(), ws.numel() * 4, N.stream_ptr())
+
+
 def _lm_rows(name, x):
     _check(x.is_cuda, f"{name} must be on the GPU (no CPU fallback), got {x.device}")
     _check(x.dtype in _DT, f"{name} dtype {x.dtype} not in {tuple(_DT)}")
@@ -589,4 +658,4 @@ def lm_head_bwd(coef: torch.Tensor, h: torch.Tensor, w: torch.Tensor, labels: to
 OPS = ("attn_fwd", "attn_bwd", "alibi_attn_qkvpacked", "flash_attn_qkvpacked", "linear_fwd",
        "transpose_bf16", "geglu_linear_fwd", "geglu_linear_dgrad",
        "geglu_fwd", "geglu_bwd", "xent_fwd", "cls_head_fwd", "cls_loss", "cls_head_bwd", "pool_head_fwd",
-       "pool_head_bwd", "lm_head_fwd", "lm_head_bwd")
+       "pool_head_bwd", "pool_head_wide_fwd", "pool_head_wide_bwd", "lm_head_fwd", "lm_head_bwd")

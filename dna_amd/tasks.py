@@ -112,6 +112,125 @@ class ConfusionMatrix:
         return {"accuracy": acc, "mcc": mcc, "f1_macro": f1_macro}
 
 
+class PearsonR:
+    """Pearson correlation per target column from float64 running sums (n, sum x, sum y, sum x^2,
+    sum y^2, sum xy per column), accumulated on the device of the inputs -- no host sync per
+    batch. compute() at the end of a split gives pearsonr_<name> per column and pearsonr_mean
+    over the pooled predictions of the split. The reference calls scipy.stats.pearsonr per batch
+    instead and averages the per-batch values (src/tasks/metrics.py:326-352)."""
+
+    def __init__(self, names=("dev", "hk")):
+        self.names = tuple(names)
+        self.reset()
+
+    def reset(self):
+        self.sums = torch.zeros(6, len(self.names), dtype=torch.float64)
+
+    def update(self, pred, target):
+        """pred, target [b, len(names)] (target in any shape with as many values)."""
+        x = pred.detach().reshape(-1, len(self.names)).to(torch.float64)
+        y = target.detach().reshape(x.shape).to(torch.float64)
+        if self.sums.device != x.device:  # once: the sums move to where the batches are
+            self.sums = self.sums.to(x.device)
+        self.sums += torch.stack([torch.ones_like(x).sum(0), x.sum(0), y.sum(0), (x * x).sum(0),
+                                  (y * y).sum(0), (x * y).sum(0)])
+
+    def compute(self):
+        n, sx, sy, sxx, syy, sxy = self.sums.cpu()
+        cov = n * sxy - sx * sy
+        den = ((n * sxx - sx * sx) * (n * syy - sy * sy)).clamp(min=0).sqrt()
+        r = torch.where(den > 0, cov / den.clamp(min=1e-300), torch.zeros_like(cov))
+        out = {f"pearsonr_{name}": v for name, v in zip(self.names, r.tolist())}
+        out["pearsonr_mean"] = r.mean().item() if len(self.names) else 0.0
+        return out
+
+
+class MultilabelAUROC:
+    """Area under the ROC curve per label, averaged over the labels (the DeepSEA paper's metric).
+    update() keeps the batch's logits (fp32) and labels (uint8) on the device of the inputs -- no
+    host sync per batch; compute() at the end of a split ranks each label's logits over the
+    pooled predictions of the split (average ranks on ties) and takes the rank-sum (Mann-Whitney)
+    AUROC: (sum of the positives' ranks - n_pos (n_pos + 1) / 2) / (n_pos n_neg). -> `roc`, the
+    mean over the labels for which both classes occur, and `roc_labels_skipped`, how many labels
+    had only one class.
+
+    Not the reference's `roc` (src/tasks/metrics.py:251-279), which softmaxes the logits across
+    the labels, scores the flattened [batch x labels] values as one binary problem with sklearn,
+    per batch, and averages the per-batch values."""
+
+    def __init__(self, num_labels):
+        self.num_labels = int(num_labels)
+        self.reset()
+
+    def reset(self):
+        self.logits, self.labels = [], []
+
+    def update(self, logits, target):
+        self.logits.append(logits.detach().reshape(-1, self.num_labels).to(torch.float32))
+        self.labels.append((target.detach().reshape(-1, self.num_labels) > 0.5).to(torch.uint8))
+
+    def compute(self):
+        if not self.logits:
+            return {"roc": 0.0, "roc_labels_skipped": self.num_labels}
+        x = torch.cat(self.logits).to(torch.float64)
+        y = torch.cat(self.labels).to(torch.float64)
+        n = x.shape[0]
+        xs, order = x.sort(dim=0, stable=True)
+        # average rank of a run of ties: (first + last 1-based position of the run) / 2
+        pos = torch.arange(1, n + 1, dtype=torch.float64, device=x.device)[:, None].expand_as(xs)
+        new = torch.ones_like(xs, dtype=torch.bool)
+        new[1:] = xs[1:] != xs[:-1]
+        first = torch.where(new, pos, torch.zeros_like(pos)).cummax(dim=0).values
+        last_of_run = torch.ones_like(new)
+        last_of_run[:-1] = new[1:]
+        big = torch.full_like(pos, float(n + 1))
+        last = torch.where(last_of_run, pos, big).flip(0).cummin(dim=0).values.flip(0)
+        ys = y.gather(0, order)
+        n_pos = ys.sum(0)
+        n_neg = n - n_pos
+        u = (ys * (first + last) / 2).sum(0) - n_pos * (n_pos + 1) / 2
+        ok = (n_pos > 0) & (n_neg > 0)
+        auc = u / (n_pos * n_neg).clamp(min=1)
+        skipped = int((~ok).sum().item())
+        roc = auc[ok].mean().item() if skipped < self.num_labels else 0.0
+        return {"roc": roc, "roc_labels_skipped": skipped}
+
+
+# task.loss of a pooling-head experiment -> (the head's problem type, what the head's loss -- a
+# mean over B x C -- is multiplied by). customMSE (reference metrics.py:354-356) is the sum over
+# the C columns of each column's mean: C times the head's loss. deepsea_loss is
+# binary_cross_entropy under another name (metrics.py:282-285).
+POOL_LOSSES = {
+    "cross_entropy": ("single_label_classification", lambda c: 1.0),
+    "mse": ("regression", lambda c: 1.0),
+    "customMSE": ("regression", lambda c: float(c)),
+    "binary_cross_entropy": ("multi_label_classification", lambda c: 1.0),
+    "deepsea_loss": ("multi_label_classification", lambda c: 1.0),
+}
+# task._name_ -> the problem type its losses must have and its default loss
+POOL_TASKS = {
+    "sequence_classification": ("single_label_classification", "cross_entropy"),
+    "regression": ("regression", "mse"),
+    "multilabel_classification": ("multi_label_classification", "binary_cross_entropy"),
+}
+
+
+def pool_loss(task_name, loss_name, num_labels):
+    """-> (problem_type, loss_scale) of a pooling-head task; an unknown task or loss, or a loss
+    of another task's kind, is a ValueError that names it."""
+    if task_name not in POOL_TASKS:
+        raise ValueError(f"task._name_={task_name!r}: one of {sorted(POOL_TASKS)}")
+    problem, default = POOL_TASKS[task_name]
+    loss_name = default if loss_name is None else loss_name
+    if loss_name not in POOL_LOSSES:
+        raise ValueError(f"task.loss={loss_name!r}: one of {sorted(POOL_LOSSES)}")
+    kind, scale = POOL_LOSSES[loss_name]
+    if kind != problem:
+        raise ValueError(f"task.loss={loss_name!r} is a {kind} loss; task._name_={task_name!r} "
+                         f"needs a {problem} one")
+    return problem, scale(num_labels)
+
+
 torchmetric_fns = {"perplexity": Perplexity, "num_tokens": NumTokens}
 
 

@@ -266,8 +266,10 @@ class _ClsSteps(ModuleTrainer):
         return loss
 
     def step(self, input_ids, labels) -> torch.Tensor:
-        """One optimizer step on one batch (ids [b, S] and labels on the device). The logits and
-        (single-label) predictions of the step stay in last_logits / last_pred; no host sync."""
+        """One optimizer step on one batch (ids [b, S] and labels on the device: int64 [b] for a
+        single-label head, fp32 [b, C] for a regression or multi-label one). The logits and
+        (single-label; None otherwise) predictions of the step stay in last_logits / last_pred;
+        no host sync."""
         return self._run([(input_ids, labels)], 1)
 
     @torch.no_grad()

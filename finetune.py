@@ -21,6 +21,15 @@ SequenceDecoder) and caduceus_cls (CaduceusForSequenceClassification) read a Gen
 folder (dataset.dest_path / dataset.dataset_name, character tokens at a fixed length), train with
 SeqClsTrainer on the fused pooling head, and share the epoch loop, metrics, events and
 checkpoints. The benchmarks have no validation split: val and test are both the test folder.
+dataset._name_ deepstarr (task regression, loss customMSE: two targets, reports loss and
+pearsonr_dev / pearsonr_hk / pearsonr_mean) and deepsea (task multilabel_classification, loss
+deepsea_loss: 919 labels on the wide pooling head, reports loss, roc and roc_labels_skipped) read
+their own train / val / test files:
+
+    python finetune.py experiment=hyena/deepstarr_hyena dataset.dest_path=/data/deepstarr
+    python finetune.py experiment=hyena/deepsea_hyena dataset.dest_path=/data/deepsea
+    python finetune.py experiment=caduceus/deepstarr_caduceus dataset.dest_path=/data/deepstarr
+
 train.pretrained_model_path there takes an LM / masked-LM checkpoint of train.py (backbone
 loaded, head fresh; dna_embedding honours train.pretrained_model_state_hook.freeze_backbone: the
 backbone then gets no update and no weight decay) or one of this script's checkpoints.
@@ -55,21 +64,34 @@ def _scheduler(cfg):
     return {k: v for k, v in cfg.scheduler.to_container().items() if k != "_name_"}
 
 
+def _metric(problem_type, num_labels):
+    """The evaluator of a problem type: (accumulator, whether it reads the logits -- or the
+    head's argmax). Single-label: accuracy, mcc, f1_macro; regression: pearsonr_dev, pearsonr_hk
+    (the DeepSTARR targets' names) and pearsonr_mean; multi-label: roc, roc_labels_skipped."""
+    from dna_amd.tasks import ConfusionMatrix, MultilabelAUROC, PearsonR
+    if problem_type == "regression":
+        names = ("dev", "hk") if num_labels == 2 else tuple(str(i) for i in range(num_labels))
+        return PearsonR(names), True
+    if problem_type == "multi_label_classification":
+        return MultilabelAUROC(num_labels), True
+    return ConfusionMatrix(num_labels), False
+
+
 @torch.no_grad()
-def evaluate(trainer, ds, batch_size, device, num_labels):
-    """-> {"loss", "accuracy", "mcc", "f1_macro"} of one split; counts stay on the device until
-    the split is done."""
-    from dna_amd.tasks import ConfusionMatrix
-    cm = ConfusionMatrix(num_labels)
+def evaluate(trainer, ds, batch_size, device, num_labels,
+             problem_type="single_label_classification"):
+    """-> {"loss", ...the problem type's metrics (_metric)} of one split; the metric's state
+    stays on the device until the split is done."""
+    metric, on_logits = _metric(problem_type, num_labels)
     total = torch.zeros((), device=device, dtype=torch.float64)
     for i in range(0, len(ds), batch_size):
         items = [ds[j] for j in range(i, min(i + batch_size, len(ds)))]
         ids, labels = ds.collate(items)
         ids, labels = ids.to(device), labels.to(device)
-        _, loss, pred = trainer.evaluate(ids, labels)
+        logits, loss, pred = trainer.evaluate(ids, labels)
         total += loss.double() * len(items)
-        cm.update(pred, labels)
-    out = cm.compute()
+        metric.update(logits if on_logits else pred, labels)
+    out = metric.compute()
     out["loss"] = (total / max(len(ds), 1)).item()
     return out
 
@@ -83,8 +105,21 @@ def _char_tokenizer(max_length, padding_side="left"):
                               padding_side=padding_side)
 
 
+def _pool_task(cfg, num_labels):
+    """-> (problem_type, loss_scale) from task._name_ and task.loss (tasks.pool_loss)."""
+    from dna_amd.tasks import pool_loss
+    task = cfg.get("task")
+    task = task.to_container() if task is not None else {}
+    loss = task.get("loss")
+    if isinstance(loss, dict):
+        loss = loss.get("_name_")
+    return pool_loss(task.get("_name_", "sequence_classification"), loss, num_labels)
+
+
 def _pool_model(cfg, num_labels, tokenizer):
-    """The model of a pooling-head experiment from cfg.model (+ cfg.decoder for dna_embedding)."""
+    """The model of a pooling-head experiment from cfg.model (+ cfg.decoder for dna_embedding);
+    its head's problem type and loss scale from cfg.task."""
+    problem, scale = _pool_task(cfg, num_labels)
     mc = {k: v for k, v in cfg.model.to_container().items() if k != "_name_"}
     if cfg.model._name_ == "dna_embedding":
         from dna_amd.decoders import SequenceClassifier
@@ -94,7 +129,8 @@ def _pool_model(cfg, num_labels, tokenizer):
         if dec.get("_name_", "sequence") != "sequence":
             raise NotImplementedError(f"decoder {dec.get('_name_')!r} (sequence only)")
         return SequenceClassifier(DNAEmbeddingModel(**mc), num_labels, mode=dec.get("mode", "pool"),
-                                  use_lengths=dec.get("use_lengths", False))
+                                  use_lengths=dec.get("use_lengths", False), problem_type=problem,
+                                  loss_scale=scale)
     from dna_amd.caduceus import CaduceusForSequenceClassification
     head = {k: mc.pop(k) for k in ("pooling_strategy", "conjoin_train", "conjoin_eval") if k in mc}
     config = mc.pop("config")
@@ -102,7 +138,8 @@ def _pool_model(cfg, num_labels, tokenizer):
         raise TypeError(f"caduceus_cls: unknown model keys {sorted(mc)}")
     if config.get("rcps") and config.get("complement_map") is None:
         config["complement_map"] = tokenizer.complement_map()
-    return CaduceusForSequenceClassification(num_labels=num_labels, **head, **config)
+    return CaduceusForSequenceClassification(num_labels=num_labels, problem_type=problem,
+                                             loss_scale=scale, **head, **config)
 
 
 def load_pretrained(model, state_dict, freeze_backbone=False):
@@ -127,10 +164,35 @@ def load_pretrained(model, state_dict, freeze_backbone=False):
     return {"missing": list(missing), "unexpected": len(unexpected)}
 
 
+POOL_DATASETS = ("genomic_benchmark", "deepstarr", "deepsea")
+
+
+def _pool_splits(ds, tok, max_length):
+    """dataset._name_ -> {"train", "dev", "test": dataset}. Genomic Benchmarks have no validation
+    split (dev is the test folder); DeepSTARR and DeepSEA have their own train / val / test
+    files."""
+    from dna_amd import finetune_data as FD
+    kw = dict(max_length=max_length, tokenizer=tok, use_padding=ds.get("use_padding", True),
+              add_eos=ds.get("add_eos", False))
+    rc = ds.get("rc_aug", False)
+    name = ds.get("_name_", "genomic_benchmark")
+    if name == "genomic_benchmark":
+        train_ds = FD.GenomicBenchmarkFolder(ds.dest_path, ds.dataset_name, "train", rc_aug=rc, **kw)
+        test_ds = FD.GenomicBenchmarkFolder(ds.dest_path, ds.dataset_name, "val",
+                                            classes=train_ds.classes, **kw)
+        return {"train": train_ds, "dev": test_ds, "test": test_ds}
+    if name == "deepstarr":
+        make = lambda split, **k: FD.DeepSTARRFolder(ds.dest_path, split, **kw, **k)
+    else:
+        make = lambda split, **k: FD.DeepSEACsv(ds.dest_path, split,
+                                                max_rows=ds.get("max_rows", 40000), **kw, **k)
+    return {"train": make("train", rc_aug=rc), "dev": make("val"), "test": make("test")}
+
+
 def finetune_pool(cfg, dry_run=False, out=sys.stdout):
-    """The dna_embedding / caduceus_cls path: Genomic Benchmarks folder, SeqClsTrainer."""
+    """The dna_embedding / caduceus_cls path: a Genomic Benchmarks folder, the DeepSTARR files or
+    the DeepSEA tables (dataset._name_), the head and its loss from cfg.task, SeqClsTrainer."""
     import train as T
-    from dna_amd.finetune_data import GenomicBenchmarkFolder
 
     if T.n_devices(cfg.trainer) != 1:
         raise NotImplementedError("finetune.py: single-GPU fine-tuning only (trainer.devices=1)")
@@ -141,28 +203,26 @@ def finetune_pool(cfg, dry_run=False, out=sys.stdout):
     sched = _scheduler(cfg)
     opt = cfg.optimizer.to_container()
     ds = cfg.dataset
+    if ds.get("_name_", "genomic_benchmark") not in POOL_DATASETS:
+        raise ValueError(f"dataset._name_={ds.get('_name_')!r}: one of {POOL_DATASETS}")
     max_length = int(ds.get("max_length", 200))
     tok = _char_tokenizer(max_length, ds.get("padding_side", "left"))
     if dry_run:
         model = _pool_model(cfg, int(ds.get("d_output") or 2), tok)
         print(json.dumps({"dry_run": True, "model": cfg.model._name_,
                           "model_params": sum(p.numel() for p in model.parameters()),
-                          "num_labels": model.num_labels, "dest_path": ds.get("dest_path"),
+                          "num_labels": model.num_labels, "problem_type": model.problem_type,
+                          "loss_scale": model.loss_scale, "dataset": ds.get("_name_"),
+                          "dest_path": ds.get("dest_path"),
                           "dataset_name": ds.get("dataset_name"),
                           "monitor": cfg.train.monitor, "mode": cfg.train.mode,
                           "scheduler": sched, "optimizer": opt}), file=out)
         return None
     if not ds.get("dest_path"):
-        raise ValueError("dataset.dest_path=<folder holding <dataset_name>/train and /test> is "
-                         "required")
-    kw = dict(max_length=max_length, tokenizer=tok, use_padding=ds.get("use_padding", True),
-              add_eos=ds.get("add_eos", False))
-    train_ds = GenomicBenchmarkFolder(ds.dest_path, ds.dataset_name, "train",
-                                      rc_aug=ds.get("rc_aug", False), **kw)
-    test_ds = GenomicBenchmarkFolder(ds.dest_path, ds.dataset_name, "val",
-                                     classes=train_ds.classes, **kw)
-    splits = {"train": train_ds, "dev": test_ds, "test": test_ds}
-    num_labels = int(ds.get("d_output") or train_ds.num_labels)
+        raise ValueError("dataset.dest_path=<folder holding the dataset's files> is required "
+                         "(genomic_benchmark: <dataset_name>/train and /test)")
+    splits = _pool_splits(ds, tok, max_length)
+    num_labels = int(ds.get("d_output") or splits["train"].num_labels)
     model = _pool_model(cfg, num_labels, tok)
     pre = cfg.train.get("pretrained_model_path")
     if pre:
@@ -277,7 +337,9 @@ def _fit(cfg, trainer, model, splits, device, out):
                 break
         metrics = {}
         for name, split in (("val", "dev"), ("test", "test")):
-            for k, v in evaluate(trainer, splits[split], ebs, device, model.num_labels).items():
+            for k, v in evaluate(trainer, splits[split], ebs, device, model.num_labels,
+                                 getattr(model, "problem_type", None)
+                                 or "single_label_classification").items():
                 metrics[f"{name}/{k}"] = v
         print(json.dumps(dict({"event": "eval", "epoch": epoch, "step": trainer.global_step},
                               **metrics)), file=out, flush=True)

@@ -609,6 +609,36 @@ int dna_pool_head_bwd(const float* dlogits, const float* upstream, const float* 
                       int64_t dx2_stride, int flip2, float* dW, float* dbias, int accumulate,
                       void* workspace, size_t workspace_bytes, void* stream);
 
+/* The wide pooling head: the same head for 1 <= C <= 1024 labels under the regression and the
+ * multi-label loss (DeepSTARR's 2 targets fit the narrow head; DeepSEA's 919 do not). Everything
+ * above holds -- the windowed mean, x2 / RCPS halves with flip and mirror, logits, the loss as
+ * dna_cls_loss computes it with the element arithmetic in double, dlogits, dW, dbias, dx1 / dx2,
+ * upstream, accumulate, 1 <= B <= 65,535, any D >= 1, fp32 or bf16 x -- except: there is no pred
+ * argument, and labels != NULL with problem_type DNA_CLS_SINGLE_LABEL is an error (no user of a
+ * wide single-label head exists). logits, gs = dlogits W and dW accumulate in double in index
+ * order, dbias sums its column in double; the loss's B x C elements are spread over the grid,
+ * their partial sums (double, in the workspace) are added in a fixed order by a finish launch.
+ * No atomics, no hand-off between workgroups inside a launch: bit-identical from run to run.
+ * dna_pool_head_wide_fwd: three launches (partial sums over chunks of L, the narrow head's kernel;
+ * chunks -> pooled; pooled -> logits, W read once per 32 sequences), plus two for the loss when
+ * labels != NULL (elements -> per-workgroup sums; their sum).
+ * dna_pool_head_wide_bwd: two launches (gs, dW and dbias; the narrow head's broadcast into dx1 /
+ * dx2), one when dx1 == NULL. */
+size_t dna_pool_head_wide_fwd_workspace(int batch, int len, int width, int labels_n);
+int dna_pool_head_wide_fwd(const void* x1, int64_t x1_stride, const void* x2, int64_t x2_stride,
+                           int flip2, int x_dtype, const int32_t* start, const int32_t* count,
+                           const float* W, const float* bias, int batch, int len, int width,
+                           int labels_n, float* pooled, float* logits, const void* labels,
+                           int problem_type, float* loss, float* dlogits, void* workspace,
+                           size_t workspace_bytes, void* stream);
+size_t dna_pool_head_wide_bwd_workspace(int batch, int len, int width, int labels_n);
+int dna_pool_head_wide_bwd(const float* dlogits, const float* upstream, const float* pooled,
+                           const float* W, const int32_t* start, const int32_t* count, int batch,
+                           int len, int width, int labels_n, int x_dtype, void* dx1,
+                           int64_t dx1_stride, void* dx2, int64_t dx2_stride, int flip2, float* dW,
+                           float* dbias, int accumulate, void* workspace, size_t workspace_bytes,
+                           void* stream);
+
 /* ------------------------------------------------------------------ small-vocabulary masked-LM head
  * The tied LM head + masked cross entropy of the HyenaDNA "blm" model (reference
  * src/models/sequence/long_conv_lm.py:578-682 lm_head, src/tasks/metrics.py:268-273
