@@ -141,6 +141,12 @@ _SIGS = {
     "dna_lm_head_bwd_workspace": (_sz, [_i, _i, _i]),
     "dna_lm_head_bwd": (_i, [_vp, _vp, _i64, _i, _vp, _i, _vp, _vp, _vp, _f, _i, _i, _i, _vp, _i64,
                              _vp, _i, _vp, _sz, _vp]),
+    "dna_lm_head_rc_fwd_workspace": (_sz, [_i, _i, _i]),
+    "dna_lm_head_rc_fwd": (_i, [_vp, _i64, _i, _vp, _i, _vp, _vp, _i, _i, _i, _f, _vp, _vp, _vp,
+                                _vp, _vp, _sz, _vp]),
+    "dna_lm_head_rc_bwd_workspace": (_sz, [_i, _i, _i]),
+    "dna_lm_head_rc_bwd": (_i, [_vp, _vp, _i64, _i, _vp, _i, _vp, _vp, _vp, _vp, _f, _i, _i, _i,
+                                _vp, _i64, _vp, _i, _vp, _sz, _vp]),
     "dna_sumsq_workspace": (_sz, [_sz]),
     "dna_sumsq": (_i, [_vp, _sz, _vp, _vp, _sz, _vp]),
     "dna_adamw_step": (_i, [_vp, _vp, _vp, _vp, _vp, _sz, _f, _f, _f, _f, _f, _i, _vp, _f, _f,

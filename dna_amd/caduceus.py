@@ -104,9 +104,14 @@ def _rc(x):
 
 def _complement_tensor(complement_map):
     """torch.tensor(list(OrderedDict(complement_map).values())) as modeling_rcps.py:27-30 builds
-    it; a list/tuple is taken as already ordered by token id."""
+    it; a list/tuple is taken as already ordered by token id. Every entry must be a token id of
+    the map itself: the kernels that index with it (csrc/lm_head.hip) do not check."""
     vals = list(complement_map.values()) if isinstance(complement_map, dict) else list(complement_map)
-    return torch.tensor(vals, dtype=torch.long)
+    cm = torch.tensor(vals, dtype=torch.long)
+    if cm.numel() and (int(cm.min()) < 0 or int(cm.max()) >= cm.numel()):
+        raise ValueError(f"complement_map entries must lie in [0, {cm.numel()}); got "
+                         f"[{int(cm.min())}, {int(cm.max())}]")
+    return cm
 
 
 class RCPSEmbedding(nn.Module):
@@ -396,6 +401,33 @@ class CaduceusForMaskedLM(nn.Module):
                                      reduction="none")
                 loss = ce.sum() / (y != ig).sum()
         return loss, logits
+
+    def mlm_loss(self, input_ids, mask, index, n_mask=None, n_unk_masked=None):
+        """The task loss bert_cross_entropy (mean CE over the masked positions against the
+        original ids) without dense [B, L, V] logits; BertLMHeadModel.mlm_loss's signature and
+        return value, `index` a hyena_lm.BlmIndex. -> (loss, compact logits | None).
+
+        Padded vocabulary <= 64 (the character tokenizer): the backbone output goes to the fused
+        head (functional.MaskedLMHead, csrc/lm_head.hip) with index.labels -- for rcps the
+        RC-equivariant one, which reads both halves of the 2 * d_model channels in place with the
+        head's complement map; no logits exist, no flipped copy of the hidden state is made, the
+        divisor is counted on the device. Larger vocabularies: the masked rows are compacted with
+        index_select, projected by self.lm_head and scored by MaskedCrossEntropy. A batch without
+        a masked position gives loss 0 and zero gradients (the dense path's mean over an empty
+        selection is NaN). loss_weights are not built here (forward() has them). With
+        tie_word_embeddings=False (rcps=False only) the head's own weight is what is read."""
+        h = self.caduceus(input_ids)
+        w = self.lm_head.weight
+        if w.shape[0] <= DF.LM_HEAD_MAX_VOCAB:
+            cm = self.lm_head.complement_map if self.config["rcps"] else None
+            loss, _ = DF.masked_lm_head(h, w, index.labels, complement_map=cm)
+            return loss, None
+        M = int(index.flat_masked.numel())
+        if M == 0:
+            return h.sum() * 0.0, None
+        rows = h.reshape(-1, h.shape[-1]).index_select(0, index.flat_masked)
+        logits = self.lm_head(rows)
+        return DF.MaskedCrossEntropy.apply(logits, index.target, M), logits
 
 
 POOLING = ("mean", "first", "last")

@@ -23,6 +23,18 @@
 // Backward: dh_kernel (the forward's cut of the rows; lane v holds coef_r,v, the lanes split D),
 // dw_part_kernel (a thread per column, a workgroup per chunk of rows: the chunk's kept rows are
 // listed in index order, then added in that order), dw_finish_kernel (chunks in index order).
+//
+// RC-equivariant head (Caduceus RCPSLMHead; dna_lm_head_rc_*): rows of 2 D channels, the tied
+// W [V, D] and a complement map cm [V]:
+//
+//   logit_v = sum_{d<D} h[r, d] W[v, d] + sum_{d<D} h[r, 2D-1-d] W[cm[v], d]
+//
+// which is the head above over 2 D channels with Wt[v, d] = W[v, d], Wt[v, D + j] =
+// W[cm[v], D-1-j]. rc_expand_kernel writes Wt (W's dtype, at most 64 x 2 D elements) into the
+// workspace, the five kernels above run unchanged at width 2 D, and rc_fold_kernel takes the
+// gradient of Wt back to W: dW[u, d] (+)= dWt[u, d] + sum over v with cm[v] == u, v ascending,
+// of dWt[v, 2D-1-d] -- the backward of the gather W[cm], whatever cm is (not an involution, not
+// injective), one thread per element, a fixed order, no atomics.
 #include <math.h>
 
 #include "common.h"
@@ -364,6 +376,40 @@ __global__ __launch_bounds__(TPB) void dw_finish_kernel(const float* part, int n
   dW[idx] = accumulate ? dW[idx] + s * scale : s * scale;
 }
 
+// Wt [V, 2 D] in W's dtype: Wt[v, d] = W[v, d], Wt[v, D + j] = W[cm[v], D-1-j]. The entries of cm
+// are validated where the map is built, on the host; one outside [0, V) reads nothing here (0).
+template <bool WBF>
+__global__ __launch_bounds__(TPB) void rc_expand_kernel(const void* W, const int64_t* cm, int D,
+                                                        int V, void* Wt) {
+  const int idx = blockIdx.x * TPB + threadIdx.x;
+  if (idx >= V * 2 * D) return;
+  const int v = idx / (2 * D), c = idx - v * 2 * D;
+  int64_t src;
+  if (c < D) {
+    src = (int64_t)v * D + c;
+  } else {
+    const int64_t u = cm[v];
+    src = u >= 0 && u < V ? u * D + (2 * D - 1 - c) : -1;
+  }
+  if constexpr (WBF) {
+    reinterpret_cast<bf16*>(Wt)[idx] = src >= 0 ? reinterpret_cast<const bf16*>(W)[src] : (bf16)0.f;
+  } else {
+    reinterpret_cast<float*>(Wt)[idx] = src >= 0 ? reinterpret_cast<const float*>(W)[src] : 0.f;
+  }
+}
+
+// dW[u, d] (+)= dWt[u, d] + sum_{v ascending, cm[v] == u} dWt[v, 2D-1-d]; a thread per (u, d)
+__global__ __launch_bounds__(TPB) void rc_fold_kernel(const float* dWt, const int64_t* cm, int D,
+                                                      int V, float* dW, int accumulate) {
+  const int idx = blockIdx.x * TPB + threadIdx.x;
+  if (idx >= V * D) return;
+  const int u = idx / D, d = idx - u * D;
+  float s = dWt[(int64_t)u * 2 * D + d];
+  for (int v = 0; v < V; ++v)
+    if (cm[v] == u) s += dWt[(int64_t)v * 2 * D + (2 * D - 1 - d)];
+  dW[idx] = accumulate ? dW[idx] + s : s;
+}
+
 // pool_head.hip's rule: 16-byte accesses when D, the row stride and the base pointers allow
 // them (the rows of the contiguous W are then 16-byte aligned in either dtype), else one element
 static int pick_vec(int dtype, int D, const void* p, int64_t stride, const void* W) {
@@ -507,5 +553,91 @@ extern "C" int dna_lm_head_bwd(const float* coef, const void* h, int64_t h_strid
                      dim3(lmh::TPB), 0, s, (const float*)workspace, nchunks, n, count, upstream,
                      denom, dW, accumulate ? 1 : 0);
   DNA_LAUNCH_CHECK("dna_lm_head_bwd");
+  return DNA_OK;
+}
+
+// ------------------------------------------------------------------------ RC-equivariant head
+// workspace of both: Wt [V, 2 D] (4 bytes per element reserved: W is fp32 or bf16) at the base,
+// then what the plain entry point takes at width 2 D (backward: dWt [V, 2 D] fp32 before it)
+static size_t rc_wt_bytes(int D, int V) { return (size_t)V * 2 * D * sizeof(float); }
+
+static int rc_check(const char* name, int T, int D, int V, int h_dtype, int w_dtype,
+                    const void* W, const int64_t* cm, const void* workspace,
+                    size_t workspace_bytes, size_t need) {
+  int st = lmh::shape_check(name, T, D, V, h_dtype, w_dtype);
+  if (st != DNA_OK) return st;
+  DNA_CHECK_ARG((int64_t)V * 2 * D <= 0x7fffffff, "%s: V * 2 D too large", name);
+  DNA_CHECK_ARG(W && cm, "%s: null pointer", name);
+  DNA_CHECK_ARG(workspace && workspace_bytes >= need && aligned(workspace, 16),
+                "%s: workspace too small or not 16-byte aligned (%zu < %zu)", name,
+                workspace_bytes, need);
+  return DNA_OK;
+}
+
+static void rc_expand(const void* W, int w_dtype, const int64_t* cm, int D, int V, void* Wt,
+                      hipStream_t s) {
+  const dim3 grid((unsigned)((V * 2 * D + lmh::TPB - 1) / lmh::TPB));
+  if (w_dtype == DNA_BF16)
+    hipLaunchKernelGGL(lmh::rc_expand_kernel<true>, grid, dim3(lmh::TPB), 0, s, W, cm, D, V, Wt);
+  else
+    hipLaunchKernelGGL(lmh::rc_expand_kernel<false>, grid, dim3(lmh::TPB), 0, s, W, cm, D, V, Wt);
+}
+
+extern "C" size_t dna_lm_head_rc_fwd_workspace(int T, int D, int V) {
+  if (T < 1 || D < 1 || V < 1) return 0;
+  return rc_wt_bytes(D, V) + dna_lm_head_fwd_workspace(T);
+}
+
+extern "C" int dna_lm_head_rc_fwd(const void* h, int64_t h_stride, int h_dtype, const void* W,
+                                  int w_dtype, const int64_t* cm, const int64_t* labels, int T,
+                                  int D, int V, float denom, float* loss_sum, int64_t* count,
+                                  float* loss, float* coef, void* workspace,
+                                  size_t workspace_bytes, void* stream) {
+  int st = rc_check("dna_lm_head_rc_fwd", T, D, V, h_dtype, w_dtype, W, cm, workspace,
+                    workspace_bytes, dna_lm_head_rc_fwd_workspace(T, D, V));
+  if (st != DNA_OK) return st;
+  DNA_CHECK_ARG(h && labels && loss_sum && count, "dna_lm_head_rc_fwd: null pointer");
+  DNA_CHECK_ARG(h_stride >= 2 * (int64_t)D, "dna_lm_head_rc_fwd: row stride must be >= 2 D");
+  rc_expand(W, w_dtype, cm, D, V, workspace, as_stream(stream));
+  DNA_LAUNCH_CHECK("dna_lm_head_rc_fwd");
+  const size_t off = rc_wt_bytes(D, V);
+  return dna_lm_head_fwd(h, h_stride, h_dtype, workspace, w_dtype, labels, T, 2 * D, V, denom,
+                         loss_sum, count, loss, coef, (char*)workspace + off,
+                         workspace_bytes - off, stream);
+}
+
+extern "C" size_t dna_lm_head_rc_bwd_workspace(int T, int D, int V) {
+  if (T < 1 || D < 1 || V < 1) return 0;
+  return 2 * rc_wt_bytes(D, V) + dna_lm_head_bwd_workspace(T, 2 * D, V);
+}
+
+extern "C" int dna_lm_head_rc_bwd(const float* coef, const void* h, int64_t h_stride, int h_dtype,
+                                  const void* W, int w_dtype, const int64_t* cm,
+                                  const int64_t* labels, const int64_t* count,
+                                  const float* upstream, float denom, int T, int D, int V,
+                                  void* dh, int64_t dh_stride, float* dW, int accumulate,
+                                  void* workspace, size_t workspace_bytes, void* stream) {
+  int st = rc_check("dna_lm_head_rc_bwd", T, D, V, h_dtype, w_dtype, W, cm, workspace,
+                    workspace_bytes, dna_lm_head_rc_bwd_workspace(T, D, V));
+  if (st != DNA_OK) return st;
+  DNA_CHECK_ARG(coef && labels && count, "dna_lm_head_rc_bwd: null pointer");
+  DNA_CHECK_ARG(!dh || dh_stride >= 2 * (int64_t)D,
+                "dna_lm_head_rc_bwd: dh row stride must be >= 2 D");
+  DNA_CHECK_ARG(!dW || (h && h_stride >= 2 * (int64_t)D),
+                "dna_lm_head_rc_bwd: dW needs h with a row stride >= 2 D");
+  hipStream_t s = as_stream(stream);
+  if (dh) {  // the only reader of Wt in the backward
+    rc_expand(W, w_dtype, cm, D, V, workspace, s);
+    DNA_LAUNCH_CHECK("dna_lm_head_rc_bwd");
+  }
+  const size_t off = rc_wt_bytes(D, V);
+  float* dWt = dW ? (float*)((char*)workspace + off) : nullptr;
+  st = dna_lm_head_bwd(coef, h, h_stride, h_dtype, workspace, w_dtype, labels, count, upstream,
+                       denom, T, 2 * D, V, dh, dh_stride, dWt, 0, (char*)workspace + 2 * off,
+                       workspace_bytes - 2 * off, stream);
+  if (st != DNA_OK || !dW) return st;
+  hipLaunchKernelGGL(lmh::rc_fold_kernel, dim3((unsigned)((V * D + lmh::TPB - 1) / lmh::TPB)),
+                     dim3(lmh::TPB), 0, s, (const float*)dWt, cm, D, V, dW, accumulate ? 1 : 0);
+  DNA_LAUNCH_CHECK("dna_lm_head_rc_bwd");
   return DNA_OK;
 }

@@ -805,18 +805,27 @@ class MaskedLMHead(torch.autograd.Function):
     count == 0 gives loss 0 and zero gradients (the reference's mean over an empty selection is
     NaN). The upstream gradient stays on the device. dh comes back in h's dtype, every element
     written by the kernel; dw is added straight into the flat gradient with FlatParams direct
-    gradients (the tied embedding adds its own share there too), else returned."""
+    gradients (the tied embedding adds its own share there too), else returned.
+
+    cm [V] int64 on the device (Caduceus' RCPSLMHead.complement_map, its entries validated on the
+    host where the module builds it): the RC-equivariant head. h is then [T, 2 D] and
+    logits = h[:, :D] w^T + flip(h[:, D:]) w[cm]^T; dw folds the gathered rows' gradient back in a
+    fixed order (dna_lm_head_rc_*)."""
 
     @staticmethod
-    def forward(ctx, h, w, labels, denom):
+    def forward(ctx, h, w, labels, denom, cm=None):
         _gpu(h, w, labels)
         ctx.set_materialize_grads(False)
         if h.dim() != 2 or h.numel() == 0:
             raise ValueError(f"dna_amd: lm head input must be a non-empty [T, D], got {tuple(h.shape)}")
-        T, D = h.shape
-        if h.stride(1) != 1 or (T > 1 and h.stride(0) < D):
+        T, Dh = h.shape
+        D = Dh if cm is None else Dh // 2
+        if cm is not None and (Dh % 2 or w.dim() != 2 or w.shape[1] != D):
+            raise ValueError(f"dna_amd: RC lm head input must have 2 * D columns for a weight "
+                             f"[V, D], got h {tuple(h.shape)}, weight {tuple(w.shape)}")
+        if h.stride(1) != 1 or (T > 1 and h.stride(0) < Dh):
             h = h.contiguous()
-        hs = h.stride(0) if T > 1 else D
+        hs = h.stride(0) if T > 1 else Dh
         V = w.shape[0]
         if w.dtype != torch.float32 or not w.is_contiguous() or tuple(w.shape) != (V, D):
             raise TypeError(f"dna_amd: lm head weight must be contiguous fp32 [V, {D}], got "
@@ -826,6 +835,12 @@ class MaskedLMHead(torch.autograd.Function):
         if labels.dtype != torch.int64 or labels.numel() != T:
             raise TypeError(f"dna_amd: lm head labels must be int64 [{T}], got {labels.dtype} "
                             f"{tuple(labels.shape)}")
+        if cm is not None:
+            _gpu(cm)
+            if cm.dtype != torch.int64 or cm.numel() != V:
+                raise TypeError(f"dna_amd: lm head complement map must be int64 [{V}], got "
+                                f"{cm.dtype} {tuple(cm.shape)}")
+            cm = cm.reshape(-1).contiguous()
         labels = labels.reshape(-1).contiguous()
         lp = getattr(w, "_dna_lp", None)
         wk = lp if (h.dtype == torch.bfloat16 and lp is not None) else w
@@ -834,14 +849,23 @@ class MaskedLMHead(torch.autograd.Function):
         out = torch.empty(2, device=dev, dtype=torch.float32)  # loss_sum, loss
         count = torch.empty((), device=dev, dtype=torch.int64)
         coef = torch.empty(T, V, device=dev, dtype=torch.float32) if need_bwd else None
-        nws = N.lib().dna_lm_head_fwd_workspace(T)
-        ws = torch.empty(max(nws // 8, 2), device=dev, dtype=torch.float64)
         dn = 0.0 if denom is None else float(denom)
-        with _timed("lm_head_fwd", float(T) * D * h.element_size(), kind="byte"):
-            N.call("dna_lm_head_fwd", h.data_ptr(), hs, _dt(h), wk.data_ptr(), _dt(wk),
-                   labels.data_ptr(), T, D, V, dn, out.data_ptr(), count.data_ptr(),
-                   out[1:].data_ptr(), _p(coef), ws.data_ptr(), ws.numel() * 8, N.stream_ptr())
-        ctx.save_for_backward(h, wk, labels, count, coef)
+        if cm is None:
+            nws = N.lib().dna_lm_head_fwd_workspace(T)
+            ws = torch.empty(max(nws // 8, 2), device=dev, dtype=torch.float64)
+            with _timed("lm_head_fwd", float(T) * D * h.element_size(), kind="byte"):
+                N.call("dna_lm_head_fwd", h.data_ptr(), hs, _dt(h), wk.data_ptr(), _dt(wk),
+                       labels.data_ptr(), T, D, V, dn, out.data_ptr(), count.data_ptr(),
+                       out[1:].data_ptr(), _p(coef), ws.data_ptr(), ws.numel() * 8, N.stream_ptr())
+        else:
+            nws = N.lib().dna_lm_head_rc_fwd_workspace(T, D, V)
+            ws = torch.empty(nws // 8 + 2, device=dev, dtype=torch.float64)
+            with _timed("lm_head_rc_fwd", float(T) * Dh * h.element_size(), kind="byte"):
+                N.call("dna_lm_head_rc_fwd", h.data_ptr(), hs, _dt(h), wk.data_ptr(), _dt(wk),
+                       cm.data_ptr(), labels.data_ptr(), T, D, V, dn, out.data_ptr(),
+                       count.data_ptr(), out[1:].data_ptr(), _p(coef), ws.data_ptr(),
+                       ws.numel() * 8, N.stream_ptr())
+        ctx.save_for_backward(h, wk, labels, count, coef, cm)
         ctx.param = w
         ctx.cfg = (hs, dn)
         ctx.mark_non_differentiable(count)
@@ -849,12 +873,12 @@ class MaskedLMHead(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dloss, dcount):
-        h, wk, labels, count, coef = ctx.saved_tensors
+        h, wk, labels, count, coef, cm = ctx.saved_tensors
         if dloss is None or coef is None:
-            return None, None, None, None
+            return None, None, None, None, None
         hs, dn = ctx.cfg
-        T, D = h.shape
-        V = wk.shape[0]
+        T, Dh = h.shape
+        V, D = wk.shape
         dev = h.device
         up = dloss.detach().to(torch.float32).reshape(1).contiguous()
         w = ctx.param
@@ -864,24 +888,36 @@ class MaskedLMHead(torch.autograd.Function):
             dw = w.grad
         elif ctx.needs_input_grad[1]:
             dw = torch.empty(V, D, device=dev, dtype=torch.float32)
-        dh = torch.empty(T, D, device=dev, dtype=h.dtype) if ctx.needs_input_grad[0] else None
-        nws = N.lib().dna_lm_head_bwd_workspace(T, D, V) if dw is not None else 0
-        ws = torch.empty(max(nws // 4, 4), device=dev, dtype=torch.float32)
-        with _timed("lm_head_bwd", float(T) * D * h.element_size(), kind="byte"):
-            N.call("dna_lm_head_bwd", coef.data_ptr(), h.data_ptr(), hs, _dt(h), wk.data_ptr(),
-                   _dt(wk), labels.data_ptr(), count.data_ptr(), up.data_ptr(), dn, T, D, V,
-                   _p(dh), D, _p(dw), int(direct), ws.data_ptr(), ws.numel() * 4, N.stream_ptr())
+        dh = torch.empty(T, Dh, device=dev, dtype=h.dtype) if ctx.needs_input_grad[0] else None
+        if cm is None:
+            nws = N.lib().dna_lm_head_bwd_workspace(T, D, V) if dw is not None else 0
+            ws = torch.empty(max(nws // 4, 4), device=dev, dtype=torch.float32)
+            with _timed("lm_head_bwd", float(T) * D * h.element_size(), kind="byte"):
+                N.call("dna_lm_head_bwd", coef.data_ptr(), h.data_ptr(), hs, _dt(h), wk.data_ptr(),
+                       _dt(wk), labels.data_ptr(), count.data_ptr(), up.data_ptr(), dn, T, D, V,
+                       _p(dh), D, _p(dw), int(direct), ws.data_ptr(), ws.numel() * 4,
+                       N.stream_ptr())
+        else:
+            nws = N.lib().dna_lm_head_rc_bwd_workspace(T, D, V)
+            ws = torch.empty(nws // 4 + 4, device=dev, dtype=torch.float32)
+            with _timed("lm_head_rc_bwd", float(T) * Dh * h.element_size(), kind="byte"):
+                N.call("dna_lm_head_rc_bwd", coef.data_ptr(), h.data_ptr(), hs, _dt(h),
+                       wk.data_ptr(), _dt(wk), cm.data_ptr(), labels.data_ptr(), count.data_ptr(),
+                       up.data_ptr(), dn, T, D, V, _p(dh), Dh, _p(dw), int(direct), ws.data_ptr(),
+                       ws.numel() * 4, N.stream_ptr())
         if direct:
             _notify_direct(w)
-            return dh, None, None, None
-        return dh, dw, None, None
+            return dh, None, None, None, None
+        return dh, dw, None, None, None
 
 
-def masked_lm_head(h, weight, labels, denom=None):
+def masked_lm_head(h, weight, labels, denom=None, complement_map=None):
     """MaskedLMHead outside autocast (the kernels take h in its own dtype, so the result is the
-    same with and without it). h [..., D], labels [...] -> (loss, count)."""
+    same with and without it). h [..., D], labels [...] -> (loss, count). complement_map [V]
+    (int64, on the device): the RC-equivariant head; h then has 2 * D columns."""
     with torch.autocast("cuda", enabled=False):
-        return MaskedLMHead.apply(h.reshape(-1, h.shape[-1]), weight, labels.reshape(-1), denom)
+        return MaskedLMHead.apply(h.reshape(-1, h.shape[-1]), weight, labels.reshape(-1), denom,
+                                  complement_map)
 
 
 # ----------------------------------------------------------------------------------- cls head

@@ -26,6 +26,9 @@ asserts (flash_attn_triton.py:849-855) -- instead of letting a kernel read out o
     torch.ops.dna_amd.pool_head_wide_bwd(... as pool_head_bwd)
     torch.ops.dna_amd.lm_head_fwd(h, w, labels, denom, loss, count, coef)
     torch.ops.dna_amd.lm_head_bwd(coef, h, w, labels, count, upstream, denom, dh, dw, accumulate)
+    torch.ops.dna_amd.lm_head_rc_fwd(h, w, cm, labels, denom, loss, count, coef)   h [T, 2 D]
+    torch.ops.dna_amd.lm_head_rc_bwd(coef, h, w, cm, labels, count, upstream, denom, dh, dw,
+                                     accumulate)
 and the reference's FlashAttention kernel slot with its own signature (flash_attn_triton.py:
 1077-1130, called at bert_layers.py:188/192 as flash_attn_qkvpacked_func(qkv, bias)), autograd
 included:
@@ -655,7 +658,65 @@ def lm_head_bwd(coef: torch.Tensor, h: torch.Tensor, w: torch.Tensor, labels: to
            N.stream_ptr())
 
 
+def _lm_rc_common(h, w, cm):
+    """The RC head's shapes: h [T, 2 D] for w [V, D], cm [V] int64 -> (T, D)."""
+    T, D2 = h.shape
+    D = w.shape[-1] if w.dim() == 2 else 0
+    _check(D > 0 and D2 == 2 * D, f"h must have 2 * D = {2 * D} columns for w [V, {D}], got {D2}")
+    _cuda_contig("cm", cm, (torch.int64,))
+    _check(cm.numel() == w.shape[0], f"cm must be int64 [{w.shape[0]}]")
+    return T, D
+
+
+@torch.library.custom_op("dna_amd::lm_head_rc_fwd", mutates_args=("loss", "count", "coef"))
+def lm_head_rc_fwd(h: torch.Tensor, w: torch.Tensor, cm: torch.Tensor, labels: torch.Tensor,
+                   denom: float, loss: torch.Tensor, count: torch.Tensor,
+                   coef: torch.Tensor | None) -> None:
+    """lm_head_fwd for the RC-equivariant head: h [T, 2 D], w [V, D], cm [V] int64 (entries in
+    [0, V), validated by the caller), logit_v = h[:, :D] w[v] + flip(h[:, D:]) w[cm[v]]."""
+    hs = _lm_rows("h", h)
+    T, D = _lm_rc_common(h, w, cm)
+    V = _lm_common(w, labels, count, T, D)
+    _cuda_contig("loss", loss, (torch.float32,))
+    _check(loss.numel() == 2, "loss must hold two fp32 values (sum, mean)")
+    if coef is not None:
+        _cuda_contig("coef", coef, (torch.float32,))
+        _check(tuple(coef.shape) == (T, V), f"coef must be [{T}, {V}]")
+    nws = N.lib().dna_lm_head_rc_fwd_workspace(T, D, V)
+    ws = torch.empty(nws // 8 + 2, device=h.device, dtype=torch.float64)
+    N.call("dna_lm_head_rc_fwd", h.data_ptr(), hs, _DT[h.dtype], w.data_ptr(), _DT[w.dtype],
+           cm.data_ptr(), labels.data_ptr(), T, D, V, float(denom), loss.data_ptr(),
+           count.data_ptr(), loss.data_ptr() + 4, _p(coef), ws.data_ptr(), ws.numel() * 8,
+           N.stream_ptr())
+
+
+@torch.library.custom_op("dna_amd::lm_head_rc_bwd", mutates_args=("dh", "dw"))
+def lm_head_rc_bwd(coef: torch.Tensor, h: torch.Tensor, w: torch.Tensor, cm: torch.Tensor,
+                   labels: torch.Tensor, count: torch.Tensor, upstream: torch.Tensor | None,
+                   denom: float, dh: torch.Tensor, dw: torch.Tensor, accumulate: bool) -> None:
+    """Backward of lm_head_rc_fwd: dh [T, 2 D] as lm_head_bwd writes it, and dw [V, D] fp32 with
+    the gradient of the gathered rows w[cm] folded back in a fixed order (accumulate: added)."""
+    hs = _lm_rows("h", h)
+    ds = _lm_rows("dh", dh)
+    T, D = _lm_rc_common(h, w, cm)
+    V = _lm_common(w, labels, count, T, D)
+    _check(dh.shape == h.shape and dh.dtype == h.dtype, "dh must match h")
+    for n, t, shape in (("coef", coef, (T, V)), ("dw", dw, (V, D))):
+        _cuda_contig(n, t, (torch.float32,))
+        _check(tuple(t.shape) == shape, f"{n} must be {shape}, got {tuple(t.shape)}")
+    if upstream is not None:
+        _cuda_contig("upstream", upstream, (torch.float32,))
+        _check(upstream.numel() == 1, "upstream must hold one fp32 value")
+    nws = N.lib().dna_lm_head_rc_bwd_workspace(T, D, V)
+    ws = torch.empty(nws // 4 + 4, device=h.device, dtype=torch.float32)
+    N.call("dna_lm_head_rc_bwd", coef.data_ptr(), h.data_ptr(), hs, _DT[h.dtype], w.data_ptr(),
+           _DT[w.dtype], cm.data_ptr(), labels.data_ptr(), count.data_ptr(), _p(upstream),
+           float(denom), T, D, V, dh.data_ptr(), ds, dw.data_ptr(), int(accumulate),
+           ws.data_ptr(), ws.numel() * 4, N.stream_ptr())
+
+
 OPS = ("attn_fwd", "attn_bwd", "alibi_attn_qkvpacked", "flash_attn_qkvpacked", "linear_fwd",
        "transpose_bf16", "geglu_linear_fwd", "geglu_linear_dgrad",
        "geglu_fwd", "geglu_bwd", "xent_fwd", "cls_head_fwd", "cls_loss", "cls_head_bwd", "pool_head_fwd",
-       "pool_head_bwd", "pool_head_wide_fwd", "pool_head_wide_bwd", "lm_head_fwd", "lm_head_bwd")
+       "pool_head_bwd", "pool_head_wide_fwd", "pool_head_wide_bwd", "lm_head_fwd", "lm_head_bwd",
+       "lm_head_rc_fwd", "lm_head_rc_bwd")

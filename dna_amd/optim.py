@@ -12,7 +12,9 @@ no limit / decay 1, the values the formula needs.
 
 ParamGroups restates the grouping of the reference's configure_optimizers (train.py:462-487):
 parameters tagged `_optim` (the Hyena filter: its own lr, weight_decay 0) get AdamW groups of
-their own. TimmCosineLRScheduler restates timm.scheduler.CosineLRScheduler with its defaults
+their own. add_optimizer_hooks restates the reference's hook that writes such `_optim` tags
+(no weight decay on biases, `_no_weight_decay` parameters, embeddings, torch norm layers;
+src/utils/optim_groups.py:14-38). TimmCosineLRScheduler restates timm.scheduler.CosineLRScheduler with its defaults
 (registry scheduler "cosine_warmup_timm"); timm is not a dependency, so nothing pins it to
 timm's output -- the same standing as the linear schedule above.
 """
@@ -22,6 +24,38 @@ import torch
 
 from . import _native as N
 from .flat import note_raw_write
+
+
+def add_optimizer_hooks(model, bias_weight_decay=False, normalization_weight_decay=False):
+    """The reference's add_optimizer_hooks (src/utils/optim_groups.py:14-38, called from
+    train.py:464-465 when train.optimizer_param_grouping is set), restated as written: walking
+    every module's named_parameters() (a module's own and its descendants'), it sets
+    `_optim = {"weight_decay": 0.0}` on
+      * parameters whose name ends in `bias`, unless bias_weight_decay;
+      * parameters tagged `_no_weight_decay` (the Mamba mixer's A_log and D);
+      * every parameter of an nn.Embedding (blacklisted regardless of the flags);
+      * every parameter of a torch normalization module (nn.LayerNorm, nn.GroupNorm, the
+        BatchNorm / InstanceNorm family, nn.LocalResponseNorm), unless normalization_weight_decay.
+    ParamGroups then gives these parameters an AdamW group of their own. As in the reference, an
+    `_optim` a layer set before (the Hyena filter's lr) is replaced where the rule applies, and a
+    tied tensor is one parameter: tagged once, whichever module reaches it.
+
+    Deviation kept on purpose: the project's RMSNorm (caduceus.RMSNorm, as mamba_ssm's) is not in
+    the reference's list, so its weight stays decayed, as it does in the reference's Caduceus
+    runs. hyena_lm.LayerNorm subclasses nn.LayerNorm and functional.HipEmbedding nn.Embedding, so
+    both fall under the rule."""
+    import torch.nn as nn
+    blacklist = (nn.Embedding,)
+    if not normalization_weight_decay:
+        blacklist += (nn.BatchNorm1d, nn.BatchNorm2d, nn.BatchNorm3d, nn.GroupNorm,
+                      nn.SyncBatchNorm, nn.InstanceNorm1d, nn.InstanceNorm2d, nn.InstanceNorm3d,
+                      nn.LayerNorm, nn.LocalResponseNorm)
+    for _, m in model.named_modules():
+        for pn, p in m.named_parameters():
+            if (not bias_weight_decay and pn.endswith("bias")) \
+                    or getattr(p, "_no_weight_decay", False) \
+                    or isinstance(m, blacklist):
+                p._optim = {"weight_decay": 0.0}
 
 
 class ParamGroups:

@@ -347,8 +347,10 @@ class SeqClsTrainer(_TorchGeneratorState, _ClsSteps):
 
 
 class BlmTrainer(_TorchGeneratorState, ModuleTrainer):
-    """Masked-LM pretraining step engine for hyena_lm.BertLMHeadModel (registry model "blm"):
-    ModuleTrainer's step -- flat fp32 parameters with the bf16 shadow under bf16 autocast,
+    """Masked-LM pretraining step engine for hyena_lm.BertLMHeadModel (registry model "blm") and
+    caduceus.CaduceusForMaskedLM (registry model "caduceus") -- any model with `mlm_loss(...)`
+    and `lm_head.weight`: ModuleTrainer's step -- flat fp32 parameters with the bf16 shadow under
+    bf16 autocast,
     gradient buckets all-reduced as the backward completes them, clip + AdamW fused -- with
     MLMTrainer's interface, which train.py drives: step(batch | [micro-batches], accum), sched,
     micro_losses, rng_state / load_rng_state, device_batch. The Hyena filter's parameters

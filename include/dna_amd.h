@@ -24,8 +24,8 @@ extern "C" {
 
 #define DNA_AMD_ABI_VERSION 1
 /* Counts additions that leave every version-1 entry point as it was (a caller built against an
- * earlier revision keeps working): 1 = dna_lm_head_*. */
-#define DNA_AMD_ABI_REVISION 1
+ * earlier revision keeps working): 1 = dna_lm_head_*, 2 = dna_lm_head_rc_*. */
+#define DNA_AMD_ABI_REVISION 2
 
 enum dna_status {
   DNA_OK = 0,
@@ -672,6 +672,31 @@ int dna_lm_head_bwd(const float* coef, const void* h, int64_t h_stride, int h_dt
                     const float* upstream, float denom, int rows, int width, int vocab, void* dh,
                     int64_t dh_stride, float* dW, int accumulate, void* workspace,
                     size_t workspace_bytes, void* stream);
+
+/* The RC-equivariant variant (Caduceus RCPSLMHead, reference
+ * src/models/caduceus/modeling_rcps.py:206-243): h [T, 2 D] (both strands' channels), the tied
+ * W [V, D] and a complement map cm [V] (device int64, entries in [0, V), validated by the caller
+ * on the host):
+ *   logit_v = sum_{d<D} h[r, d] W[v, d] + sum_{d<D} h[r, 2D-1-d] W[cm[v], d]
+ * i.e. the head above over 2 D channels with Wt[v, d] = W[v, d], Wt[v, D + j] = W[cm[v], D-1-j];
+ * Wt (W's dtype) is written into the workspace and the kernels above run at width 2 D. loss_sum,
+ * count, loss, coef, dh [T, 2 D], denom and upstream are as above. The weight gradient is folded
+ * back in a fixed order, without atomics:
+ *   dW[u, d] (+)= dWt[u, d] + sum over v with cm[v] == u, v ascending, of dWt[v, 2D-1-d]
+ * (the backward of the gather W[cm]; cm need not be an involution or injective). `width` is D, the
+ * width of W; row strides are >= 2 D. The workspace must be 16-byte aligned. Forward 3 launches,
+ * backward 1 + 1 (dh) + 2 + 1 (dW). */
+size_t dna_lm_head_rc_fwd_workspace(int rows, int width, int vocab);
+int dna_lm_head_rc_fwd(const void* h, int64_t h_stride, int h_dtype, const void* W, int w_dtype,
+                       const int64_t* cm, const int64_t* labels, int rows, int width, int vocab,
+                       float denom, float* loss_sum, int64_t* count, float* loss, float* coef,
+                       void* workspace, size_t workspace_bytes, void* stream);
+size_t dna_lm_head_rc_bwd_workspace(int rows, int width, int vocab);
+int dna_lm_head_rc_bwd(const float* coef, const void* h, int64_t h_stride, int h_dtype,
+                       const void* W, int w_dtype, const int64_t* cm, const int64_t* labels,
+                       const int64_t* count, const float* upstream, float denom, int rows,
+                       int width, int vocab, void* dh, int64_t dh_stride, float* dW,
+                       int accumulate, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------ optimizer (flat buffers)
  * Lightning gradient_clip_val=1.0 (torch.nn.utils.clip_grad_norm_) + torch AdamW

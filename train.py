@@ -7,8 +7,10 @@ train() :668-694 -> Lightning fit) for the DNABERT-2 MLM path, without Hydra or 
     `--config-dir` may point at the reference's own configs/ tree, which composes unchanged;
   * registries: model "dnabert2" -> dna_amd.bert_layers.BertForMaskedLM (src/utils/registry.py:39),
     model "blm" -> dna_amd.hyena_lm.BertLMHeadModel (HyenaDNA masked-LM pretraining: BlmTrainer,
-    the fused small-vocabulary head, `_optim` AdamW groups), schedulers "linear_warmup" and
-    "cosine_warmup_timm",
+    the fused small-vocabulary head, `_optim` AdamW groups), model "caduceus" ->
+    dna_amd.caduceus.CaduceusForMaskedLM (src/utils/registry.py:37; the same trainer, the
+    RC-equivariant fused head for rcps, `train.optimizer_param_grouping` -> no weight decay on
+    A_log / D / biases / embeddings), schedulers "linear_warmup" and "cosine_warmup_timm",
     dataset "bert_hg38" -> dna_amd.hg38.BertHG38, "dnabert2_pretrain" (text corpus) ->
     dna_amd.corpus.DNABERT2Pretrain, task "hg38" + loss "bert_cross_entropy";
   * loop: MLMTrainer steps (fused loss, bucketed RCCL all-reduce, clip + AdamW, LR schedule per
@@ -49,9 +51,11 @@ sys.path.insert(0, ROOT)
 from dna_amd.compose import compose  # noqa: E402
 
 MODEL_REGISTRY = {"dnabert2": "dna_amd.bert_layers.BertForMaskedLM",
-                  "blm": "dna_amd.hyena_lm.BertLMHeadModel"}
+                  "blm": "dna_amd.hyena_lm.BertLMHeadModel",
+                  "caduceus": "dna_amd.caduceus.CaduceusForMaskedLM"}
 # the step engine that goes with each registry model
-TRAINER_REGISTRY = {"dnabert2": "dna_amd.trainer.MLMTrainer", "blm": "dna_amd.trainer.BlmTrainer"}
+TRAINER_REGISTRY = {"dnabert2": "dna_amd.trainer.MLMTrainer", "blm": "dna_amd.trainer.BlmTrainer",
+                    "caduceus": "dna_amd.trainer.BlmTrainer"}
 SCHEDULERS = ("linear_warmup", "cosine_warmup_timm")
 
 
@@ -83,10 +87,18 @@ def build_dataset(cfg):
     return ds
 
 
+def on_module_trainer(name):
+    """Registry models whose step engine is BlmTrainer (the module trainer: bf16 autocast over
+    fp32 master weights, `_optim` AdamW groups, either schedule)."""
+    return TRAINER_REGISTRY.get(name, "").endswith(".BlmTrainer")
+
+
 def build_model(cfg, precision):
-    """The registry model of cfg.model. "dnabert2" takes its `config:` sub-key; "blm" is built
-    from cfg.model's own keys (the reference's blm block has no `config:`), and keys LMBackbone
-    refuses keep raising."""
+    """The registry model of cfg.model. "dnabert2" and "caduceus" take their `config:` sub-key
+    (the one the Caduceus fine-tuning configs use; with rcps set and complement_map null the map
+    comes from the character tokenizer, as in finetune.py); "blm" is built from cfg.model's own
+    keys (the reference's blm block has no `config:`), and keys LMBackbone refuses keep
+    raising."""
     name = cfg.model._name_
     if name not in MODEL_REGISTRY:
         raise KeyError(f"model._name_={name!r} is not in train.py's registry "
@@ -94,6 +106,17 @@ def build_model(cfg, precision):
     model_cls = _import(MODEL_REGISTRY[name])
     if name == "dnabert2":
         return model_cls(config=cfg.model.config.to_container(), precision=precision)
+    if name == "caduceus":
+        config = cfg.model.config.to_container()
+        if config.get("rcps") and config.get("complement_map") is None:
+            if cfg.dataset.get("tokenizer_name", "char") != "char":
+                raise ValueError("model.config.rcps without a complement_map needs the character "
+                                 f"tokenizer (dataset.tokenizer_name="
+                                 f"{cfg.dataset.get('tokenizer_name')!r})")
+            from dna_amd.tokenizer import CharacterTokenizer
+            config["complement_map"] = CharacterTokenizer(
+                ["A", "C", "G", "T", "N"], int(cfg.dataset.get("max_length", 1024)) + 2).complement_map()
+        return model_cls(**config)
     kw = {k: v for k, v in cfg.model.to_container().items() if k != "_name_"}
     return model_cls(**kw)
 
@@ -346,8 +369,8 @@ def train(cfg, dry_run=False, out=sys.stdout):
     if str(tr.get("accelerator", "gpu")) not in ("gpu", "cuda", "auto"):
         raise RuntimeError(f"trainer.accelerator={tr.accelerator!r}: dna_amd runs the hot path "
                            "on MI355X GPUs only (no CPU fallback)")
-    is_blm = cfg.model._name_ == "blm"
-    precision = _precision(tr.get("precision", "bf16"), fp16_as_bf16=is_blm)
+    on_module = on_module_trainer(cfg.model._name_)  # blm, caduceus: the models on BlmTrainer
+    precision = _precision(tr.get("precision", "bf16"), fp16_as_bf16=on_module)
     model = build_model(cfg, precision)
     pre = cfg.train.get("pretrained_model_path")
     if pre:
@@ -355,6 +378,17 @@ def train(cfg, dry_run=False, out=sys.stdout):
             load_lightning_state(model, pre, bool(cfg.train.get("pretrained_model_strict_load", True)))
         else:
             warnings.warn(f"train.pretrained_model_path {pre} not found; starting from init")
+    grouping = cfg.train.get("optimizer_param_grouping")
+    if grouping is not None:
+        # the reference's add_optimizer_hooks (train.py:464-465): no weight decay on biases,
+        # `_no_weight_decay` parameters, embeddings and torch normalization layers
+        if on_module:
+            from dna_amd.optim import add_optimizer_hooks
+            add_optimizer_hooks(model, **(grouping.to_container() if hasattr(grouping, "to_container")
+                                          else dict(grouping)))
+        else:
+            warnings.warn(f"train.optimizer_param_grouping is ignored for model "
+                          f"{cfg.model._name_!r}: its trainer steps one AdamW group")
     ds = build_dataset(cfg)
     ds.setup()
     task = _import("dna_amd.tasks.registry")[cfg.task._name_]
@@ -363,7 +397,7 @@ def train(cfg, dry_run=False, out=sys.stdout):
     if "scheduler" in cfg and cfg.scheduler is not None:
         sc = {k: v for k, v in cfg.scheduler.to_container().items() if k != "_name_"}
         if cfg.scheduler._name_ not in SCHEDULERS or \
-                (cfg.scheduler._name_ != "linear_warmup" and not is_blm):
+                (cfg.scheduler._name_ != "linear_warmup" and not on_module):
             raise NotImplementedError(f"scheduler {cfg.scheduler._name_!r} "
                                       f"({', '.join(SCHEDULERS)}; dnabert2: linear_warmup only)")
         sched = sc
@@ -372,7 +406,7 @@ def train(cfg, dry_run=False, out=sys.stdout):
         info = {"dry_run": True, "model_params": sum(p.numel() for p in model.parameters()),
                 "train_windows": len(ds.dataset_train), "task": task.loss_name,
                 "scheduler": sched, "optimizer": opt.to_container()}
-        if is_blm:
+        if on_module:
             from dna_amd.optim import ParamGroups
             info.update(model=cfg.model._name_, scheduler_name=cfg.scheduler._name_ if sched else None,
                         param_groups=len(ParamGroups(model)))
@@ -406,7 +440,7 @@ def train(cfg, dry_run=False, out=sys.stdout):
                       betas=tuple(opt.get("betas", (0.9, 0.999))),
                       max_grad_norm=float(tr.get("gradient_clip_val", 0.0) or 0.0),
                       scheduler=sched, seed=seed, wire_dtype=wire)
-    if is_blm:
+    if on_module:
         trainer_kw.update(scheduler_name=cfg.scheduler._name_ if sched else None,
                           autocast=torch.bfloat16 if precision == "bf16" else None)
         if opt.get("eps") is not None:
