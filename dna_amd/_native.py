@@ -31,6 +31,10 @@ _SIGS = {
     "dna_attn_bwd_ex": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp]),
     "dna_attn_bwd_var": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp, _i, _vp]),
     "dna_attn_dbias_part_rows": (_i, [_i, _i]),
+    "dna_attn_varlen_fwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp]),
+    "dna_attn_varlen_bwd_workspace": (_sz, [_i, _i, _i, _i]),
+    "dna_attn_varlen_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _vp,
+                                 _vp, _vp]),
     "dna_flash_lse_rows": (_i, [_i]),
     "dna_flash_fwd": (_i, [_vp, _i, _vp, _i, _i, _i64, _i64, _i64, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp]),
     "dna_flash_bwd": (_i, [_vp, _i, _vp, _i, _i, _i64, _i64, _i64, _vp, _vp, _vp, _i, _i, _i, _i, _i,

@@ -9,8 +9,10 @@ src.models.DNABERT2.bert_layers.BertForMaskedLM (src/utils/registry.py:39):
     bert_layers.py:756-843), including the last-layer subset computation (:469-488), the
     zero logit rows for masked [UNK] tokens, and the -10000 key-pad bias.
 Differences by design (documented in DESIGN.md): the pad mask comes from `ids != pad_token`
-without reloading the tokenizer each forward (reference :786-787); the batch stays in padded
-layout (no unpad/pad round trips) because pad keys are excluded inside the attention kernel.
+without reloading the tokenizer each forward (reference :786-787); by default the batch stays in
+padded layout (no unpad/pad round trips) because pad keys are excluded inside the attention
+kernel. With `packed=` (a PackedIndex built on the host) the encoder runs the reference's unpadded
+layout instead: the real tokens only, attention per sequence from cu_seqlens.
 
 Compute precision: "bf16" (default; MFMA bf16 kernels, fp32 master weights / LayerNorm /
 residual stream, like PL `precision: bf16` autocast) or "fp32" (exact-fp32 kernels; the 1e-3
@@ -209,24 +211,38 @@ class _HipEncoder:
             if not torch.equal(attention_mask.bool(), input_ids != self.config.pad_token_id_mask):
                 raise NotImplementedError("attention_mask must equal input_ids != [PAD]")
 
-    def encode(self, input_ids: torch.Tensor, last_rows: Optional[torch.Tensor] = None):
+    def encode(self, input_ids: torch.Tensor, last_rows: Optional[torch.Tensor] = None,
+               packed: Optional["PackedIndex"] = None):
         """Embeddings + encoder -> (x fp32, x compute dtype) of the last layer, rows flattened
         over (b, s). last_rows (flattened row indices): the last layer's output projection, MLP
         and LayerNorms run on those rows only and the result holds just them (reference
         :469-488 `subset_mask`). bf16 mode with S % 64 != 0 (the attention kernel's tile): the ids
         are padded with [PAD] to the next multiple of 64 and the outputs sliced back -- pad keys
-        are excluded in the kernel and ALiBi depends on i - j only, so valid rows are unchanged."""
+        are excluded in the kernel and ALiBi depends on i - j only, so valid rows are unchanged.
+        packed (a PackedIndex of input_ids, on its device): the reference's unpadded layout
+        (unpad_input after the embeddings' gather). Only the T = packed.total real tokens have
+        rows: the ids are gathered with packed.indices, every row-wise op runs on T rows, attention
+        is the packed kernel, and neither key_valid nor the pad-to-64 step exists. last_rows stays
+        in flattened (b, s) coordinates, names real tokens only (a [PAD] has no packed row) and is
+        mapped through packed.row_of on the device; the result holds the T packed rows (or the
+        subset rows). Dropout draws T * width counters, so its stream
+        differs from the padded run's."""
         cfg = self.config
         bert = self._bert_model()
         b, S0 = input_ids.shape
         bf16 = self.precision == "bf16"
         S = S0
-        if bf16 and S0 % 64:
+        if packed is not None:
+            packed.check(input_ids)
+            input_ids = input_ids.reshape(-1).index_select(0, packed.indices)
+            if last_rows is not None:
+                last_rows = packed.row_of.index_select(0, last_rows)
+        elif bf16 and S0 % 64:
             S = (S0 + 63) // 64 * 64
             input_ids = torch.nn.functional.pad(input_ids, (0, S - S0), value=cfg.pad_token_id_mask)
             if last_rows is not None:
                 last_rows = torch.div(last_rows, S0, rounding_mode="floor") * S + last_rows % S0
-        T = b * S
+        T = b * S if packed is None else packed.total
         H = cfg.num_attention_heads
         train = self.training
         rng = self.dropout_rng
@@ -235,7 +251,7 @@ class _HipEncoder:
             raise NotImplementedError("attention-probability dropout (reference default 0.0)")
         eps = cfg.layer_norm_eps
         ids = input_ids.reshape(-1)
-        key_valid = (ids != cfg.pad_token_id_mask).to(torch.uint8)
+        key_valid = None if packed is not None else (ids != cfg.pad_token_id_mask).to(torch.uint8)
 
         emb = bert.embeddings
         seed, off = rng.take(T * cfg.hidden_size) if p_hidden else (0, 0)
@@ -248,8 +264,11 @@ class _HipEncoder:
         for i, layer in enumerate(bert.encoder.layer):
             att = layer.attention
             qkv = self._linear(xin, att.self.Wqkv.weight, att.self.Wqkv.bias)
-            ctx = DF.alibi_attention(qkv, key_valid, slopes, b, S, H,
-                                     bias_grad=att.self.Wqkv.bias is not None)
+            if packed is not None:
+                ctx = DF.alibi_attention_varlen(qkv, packed, slopes, H)
+            else:
+                ctx = DF.alibi_attention(qkv, key_valid, slopes, b, S, H,
+                                         bias_grad=att.self.Wqkv.bias is not None)
             res = x32
             if i == L - 1 and last_rows is not None:  # output + MLP on the subset rows (:480-488)
                 ctx = ctx.index_select(0, last_rows)
@@ -279,7 +298,7 @@ class _HipEncoder:
             xin = xb if bf16 else x32
         if L == 0 and last_rows is not None:
             x32, xin = x32.index_select(0, last_rows), xin.index_select(0, last_rows)
-        if last_rows is None and S != S0:
+        if packed is None and last_rows is None and S != S0:
             d = x32.shape[1]
             x32 = x32.view(b, S, d)[:, :S0].reshape(b * S0, d)
             xin = xin.view(b, S, d)[:, :S0].reshape(b * S0, d)
@@ -308,14 +327,25 @@ class BertModel(nn.Module, _HipEncoder):
         return self
 
     def forward(self, input_ids, token_type_ids=None, attention_mask=None, position_ids=None,
-                output_all_encoded_layers=False, masked_tokens_mask=None, **kwargs):
+                output_all_encoded_layers=False, masked_tokens_mask=None, packed=None, **kwargs):
         """-> (sequence_output [b, S, hidden] fp32 with zero rows at [PAD] positions, like the
-        reference's pad_input, pooled_output [b, hidden] fp32 or None)."""
+        reference's pad_input, pooled_output [b, hidden] fp32 or None). packed (a PackedIndex of
+        input_ids): the encoder runs on the real tokens only and the rows are scattered back
+        through packed.indices into zeros -- the same outputs."""
         if output_all_encoded_layers or masked_tokens_mask is not None:
             raise NotImplementedError("BertModel.forward: last layer only, no masked_tokens_mask "
                                       "(the MLM subset path is BertForMaskedLM.mlm_logits)")
         self._check_inputs(input_ids, token_type_ids, attention_mask)
         b, S = input_ids.shape
+        if packed is not None:
+            x32, xin = self.encode(input_ids, packed=packed)
+            seq = torch.zeros(b * S, x32.shape[1], device=x32.device, dtype=x32.dtype)
+            seq = seq.index_copy(0, packed.indices, x32).view(b, S, -1)
+            pooled = None
+            if self.pooler is not None:
+                pooled = DF.pooler(xin.index_select(0, packed.cls_rows()),
+                                   self.pooler.dense.weight, self.pooler.dense.bias)
+            return seq, pooled
         x32, xin = self.encode(input_ids)
         valid = (input_ids != self.config.pad_token_id_mask).unsqueeze(-1)
         seq = x32.view(b, S, -1) * valid
@@ -382,6 +412,73 @@ class MLMIndex:
                           (self.subset_idx, self.head_idx, self.target, self.flat_masked)))
 
 
+@dataclass
+class PackedIndex:
+    """Where the real tokens of a padded batch [b, S] sit, computable on the host while the
+    batch is collated (`.to(device, non_blocking=True)` afterwards: the step has no device sync).
+    It is what the reference's bert_padding.unpad_input returns, plus the columns ALiBi needs.
+
+    indices      [T] int64  flattened (b, s) positions of the non-pad tokens, row-major
+    cu_seqlens   [b+1] int32  cumulative sequence lengths
+    positions    [T] int32  the column s of each kept token (ALiBi's |i - j| is taken in padded
+                 coordinates: a [PAD] inside a row is not a shift, so the kernel is given the
+                 columns instead of recomputing them from cu_seqlens)
+    row_of       [b*S] int64  packed row of each flattened position, -1 at pads
+    max_seqlen, total (= T), batch, seqlen: ints; first_valid: column 0 of every row is a token;
+    sq_sum: sum of the squared lengths (the attention FLOP count of the op timer)
+    """
+    indices: torch.Tensor
+    cu_seqlens: torch.Tensor
+    positions: torch.Tensor
+    row_of: torch.Tensor
+    max_seqlen: int
+    total: int
+    batch: int
+    seqlen: int
+    first_valid: bool
+    sq_sum: int = 0
+
+    @staticmethod
+    def build(input_ids, pad_token_id=PAD_TOKEN_ID):
+        if input_ids.dim() != 2:
+            raise ValueError(f"PackedIndex.build: input_ids must be [b, S], got "
+                             f"{tuple(input_ids.shape)}")
+        b, S = input_ids.shape
+        valid = input_ids != pad_token_id
+        lens = valid.sum(1)
+        empty = torch.nonzero(lens == 0).flatten()
+        if empty.numel():
+            raise ValueError(f"PackedIndex.build: row {int(empty[0])} has no real token (a "
+                             "sequence of [PAD] only has no query and no [CLS] row)")
+        indices = torch.nonzero(valid.reshape(-1)).flatten()
+        total = int(indices.numel())
+        cu = torch.zeros(b + 1, dtype=torch.int32, device=input_ids.device)
+        cu[1:] = torch.cumsum(lens, 0)
+        row_of = torch.full((b * S,), -1, dtype=torch.int64, device=input_ids.device)
+        row_of[indices] = torch.arange(total, device=input_ids.device)
+        lens_l = lens.tolist()
+        return PackedIndex(indices, cu, (indices % S).to(torch.int32), row_of, max(lens_l), total,
+                           b, S, bool(valid[:, 0].all()), sum(n * n for n in lens_l))
+
+    def to(self, device, non_blocking=False):
+        t = [x.to(device, non_blocking=non_blocking)
+             for x in (self.indices, self.cu_seqlens, self.positions, self.row_of)]
+        return PackedIndex(*t, self.max_seqlen, self.total, self.batch, self.seqlen,
+                           self.first_valid, self.sq_sum)
+
+    def check(self, input_ids):
+        if tuple(input_ids.shape) != (self.batch, self.seqlen):
+            raise ValueError(f"PackedIndex of a [{self.batch}, {self.seqlen}] batch used with "
+                             f"input_ids {tuple(input_ids.shape)}")
+
+    def cls_rows(self):
+        """Packed rows of column 0 of every sequence (the [CLS] rows), on the index's device."""
+        if not self.first_valid:
+            raise ValueError("packed batch: a row starts with [PAD]; the reference reads column 0 "
+                             "of every sequence, and a pad there has no packed row")
+        return self.row_of[::self.seqlen]
+
+
 class BertForMaskedLM(nn.Module, _HipEncoder):
     """Registry "dnabert2" model (reference bert_layers.py:691-850)."""
 
@@ -406,10 +503,13 @@ class BertForMaskedLM(nn.Module, _HipEncoder):
         return self.cls.predictions.decoder
 
     # -- the hot path ------------------------------------------------------------------------
-    def mlm_logits(self, input_ids: torch.Tensor, index: MLMIndex) -> torch.Tensor:
-        """Compact logits [M, V] of the masked rows (row-major over (b, s)), compute dtype."""
+    def mlm_logits(self, input_ids: torch.Tensor, index: MLMIndex,
+                   packed: Optional["PackedIndex"] = None) -> torch.Tensor:
+        """Compact logits [M, V] of the masked rows (row-major over (b, s)), compute dtype.
+        packed: run the encoder on the real tokens only (index.subset_idx holds valid positions
+        only, so each has a packed row)."""
         bf16 = self.precision == "bf16"
-        _, xin = self.encode(input_ids, index.subset_idx)
+        _, xin = self.encode(input_ids, index.subset_idx, packed=packed)
         seq = xin.index_select(0, index.head_idx)
         tr = self.cls.predictions.transform
         t = self._linear(seq, tr.dense.weight)
@@ -419,11 +519,11 @@ class BertForMaskedLM(nn.Module, _HipEncoder):
         return self._linear(tb if bf16 else t32, dec.weight, dec.bias)
 
     def mlm_loss(self, input_ids, mask, index: MLMIndex, n_mask: Optional[int] = None,
-                 n_unk_masked: Optional[int] = None):
+                 n_unk_masked: Optional[int] = None, packed: Optional["PackedIndex"] = None):
         """Task loss bert_cross_entropy (src/tasks/metrics.py:268-273) without dense logits:
         masked rows with label 0 ([UNK]) have all-zero logits in the reference (no gradient,
         loss ln V each); they are added as a constant."""
-        logits = self.mlm_logits(input_ids, index)
+        logits = self.mlm_logits(input_ids, index, packed=packed)
         if n_mask is None:
             n_mask = int(mask.sum())
         if n_unk_masked is None:
@@ -516,13 +616,22 @@ class BertForSequenceClassification(nn.Module, _HipEncoder):
                 cfg.problem_type = "multi_label_classification"
         return cfg.problem_type
 
-    def cls_logits(self, input_ids, labels=None, full_last_layer=False):
+    def cls_logits(self, input_ids, labels=None, full_last_layer=False, packed=None):
         """(logits [b, num_labels] fp32, loss | None, pred | None). full_last_layer: run the last
         layer on every row and read the [CLS] rows of its output in place (the reference's
-        computation; the default restricts the last layer to those rows)."""
+        computation; the default restricts the last layer to those rows). packed (a PackedIndex
+        of input_ids): the encoder runs on the real tokens only; ValueError if a row starts with
+        [PAD], whose column 0 has no packed row."""
         b, S = input_ids.shape
         rows = torch.arange(b, device=input_ids.device) * S
-        if full_last_layer:
+        if packed is not None:
+            cls_rows = packed.cls_rows()  # raises unless every row starts with a real token
+            if full_last_layer:
+                _, xin = self.encode(input_ids, packed=packed)
+                x = xin.index_select(0, cls_rows)
+            else:
+                _, x = self.encode(input_ids, rows, packed=packed)
+        elif full_last_layer:
             _, xin = self.encode(input_ids)
             x = xin.view(b, S, -1)[:, 0]
         else:
@@ -535,9 +644,9 @@ class BertForSequenceClassification(nn.Module, _HipEncoder):
 
     def forward(self, input_ids=None, attention_mask=None, token_type_ids=None, position_ids=None,
                 head_mask=None, inputs_embeds=None, labels=None, output_attentions=None,
-                output_hidden_states=None, return_dict=None):
+                output_hidden_states=None, return_dict=None, packed=None):
         self._check_inputs(input_ids, token_type_ids, attention_mask)
-        logits, loss, self.last_pred = self.cls_logits(input_ids, labels)
+        logits, loss, self.last_pred = self.cls_logits(input_ids, labels, packed=packed)
         if return_dict is not None and not return_dict:
             return ((loss, logits) if loss is not None else (logits,))
         return SequenceClassifierOutput(loss=loss, logits=logits, hidden_states=None,

@@ -66,8 +66,15 @@ class SequenceClassificationCSV(torch.utils.data.Dataset):
     def pad_token_id(self):
         return self.tokenizer.pad_token_id
 
-    def collate(self, items):
-        return collate_padded(items, self.pad_token_id)
+    def collate(self, items, unpad=False):
+        """-> (ids, labels), padded to a multiple of 64 (collate_padded). unpad: (ids, labels,
+        PackedIndex) for the packed encoder path; the width is then the batch maximum as it is --
+        the rectangle only carries the ids, no kernel runs on its [PAD] cells."""
+        if not unpad:
+            return collate_padded(items, self.pad_token_id)
+        from .bert_layers import PackedIndex
+        ids, labels = collate_padded(items, self.pad_token_id, multiple=1)
+        return ids, labels, PackedIndex.build(ids, self.pad_token_id)
 
 
 def collate_padded(items, pad_token_id=3, multiple=64):

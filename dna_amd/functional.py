@@ -715,6 +715,73 @@ def alibi_attention(qkv, key_valid, slopes, b, S, H, scale=None, bias_grad=False
                                 scale if scale is not None else 1.0 / math.sqrt(D), bias_grad)
 
 
+class AlibiAttentionVarlen(torch.autograd.Function):
+    """AlibiAttention on an unpadded batch: qkv [T, 3*H*D] holds the real tokens only, sequence n
+    owns rows cu_seqlens[n] .. cu_seqlens[n+1]-1 and attends within itself; the ALiBi distance is
+    taken between `positions` (each token's column in the padded rectangle)."""
+
+    @staticmethod
+    def forward(ctx, qkv, cu_seqlens, positions, slopes, nseq, max_seqlen, sq_sum, H, scale):
+        _gpu(qkv, cu_seqlens, positions, slopes)
+        qkv = qkv.contiguous()
+        T = qkv.shape[0]
+        D = qkv.shape[1] // (3 * H)
+        out = torch.empty(T, H * D, device=qkv.device, dtype=qkv.dtype)
+        lse = torch.empty(H, T, device=qkv.device, dtype=torch.float32)
+        with _timed("attn_varlen_fwd", 4.0 * H * sq_sum * D):
+            N.call("dna_attn_varlen_fwd", qkv.data_ptr(), cu_seqlens.data_ptr(), _p(positions),
+                   slopes.data_ptr(), nseq, T, max_seqlen, H, D, _dt(qkv), scale, out.data_ptr(),
+                   lse.data_ptr(), N.stream_ptr())
+        ctx.save_for_backward(qkv, out, lse, cu_seqlens, positions, slopes)
+        ctx.cfg = (nseq, max_seqlen, sq_sum, H, D, scale)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        qkv, out, lse, cu_seqlens, positions, slopes = ctx.saved_tensors
+        nseq, max_seqlen, sq_sum, H, D, scale = ctx.cfg
+        T = qkv.shape[0]
+        dqkv = torch.empty_like(qkv)
+        nws = N.lib().dna_attn_varlen_bwd_workspace(nseq, T, max_seqlen, H)
+        ws = torch.empty(nws, device=qkv.device, dtype=torch.uint8)
+        dout = dout.contiguous()
+        with _timed("attn_varlen_bwd", 10.0 * H * sq_sum * D):
+            N.call("dna_attn_varlen_bwd", qkv.data_ptr(), out.data_ptr(), dout.data_ptr(),
+                   lse.data_ptr(), cu_seqlens.data_ptr(), _p(positions), slopes.data_ptr(), nseq, T,
+                   max_seqlen, H, D, _dt(qkv), scale, dqkv.data_ptr(), ws.data_ptr(),
+                   N.stream_ptr())
+        return dqkv, None, None, None, None, None, None, None, None
+
+
+def _check_varlen_index(T, cu_seqlens, positions, nseq):
+    if cu_seqlens.dtype != torch.int32 or cu_seqlens.numel() != nseq + 1 or \
+            not cu_seqlens.is_contiguous():
+        raise ValueError(f"cu_seqlens must be contiguous int32 [{nseq + 1}], got "
+                         f"{cu_seqlens.dtype} {tuple(cu_seqlens.shape)}")
+    if positions is not None and (positions.dtype != torch.int32 or positions.numel() != T
+                                  or not positions.is_contiguous()):
+        raise ValueError(f"positions must be contiguous int32 [{T}], got {positions.dtype} "
+                         f"{tuple(positions.shape)}")
+
+
+def alibi_attention_varlen(qkv, packed, slopes, H, scale=None):
+    """Packed attention on the T = packed.total real tokens of a batch. `packed`: a PackedIndex
+    (dna_amd.bert_layers) already on qkv's device, or anything with its cu_seqlens / positions /
+    batch / max_seqlen / total (and optionally sq_sum, the sum of squared lengths, for the op
+    timer's FLOP count -- a host int, so nothing here waits for the device)."""
+    T = qkv.shape[0]
+    D = qkv.shape[1] // (3 * H)
+    if packed.total != T:
+        raise ValueError(f"alibi_attention_varlen: qkv has {T} rows, the index {packed.total}")
+    _check_varlen_index(T, packed.cu_seqlens, packed.positions, packed.batch)
+    sq_sum = getattr(packed, "sq_sum", None)
+    if sq_sum is None:
+        sq_sum = packed.batch * packed.max_seqlen ** 2
+    return AlibiAttentionVarlen.apply(qkv, packed.cu_seqlens, packed.positions, slopes,
+                                      packed.batch, packed.max_seqlen, sq_sum, H,
+                                      scale if scale is not None else 1.0 / math.sqrt(D))
+
+
 # ----------------------------------------------------------------------------------- GeGLU
 def _geglu_forward(g, p, seed, off):
     """(a, fac): the GeGLU output and the backward factors fac = [d a / d g1 | d a / d g2]

@@ -8,6 +8,10 @@ asserts (flash_attn_triton.py:849-855) -- instead of letting a kernel read out o
 
     torch.ops.dna_amd.attn_fwd(qkv, key_valid, slopes, b, S, H, scale, out, lse)
     torch.ops.dna_amd.attn_bwd(qkv, out, dout, lse, key_valid, slopes, b, S, H, scale, dqkv)
+    torch.ops.dna_amd.attn_varlen_fwd(qkv, cu_seqlens, positions, slopes, max_seqlen, H, scale, out,
+                                      lse)                        packed rows, per-sequence keys
+    torch.ops.dna_amd.attn_varlen_bwd(qkv, out, dout, lse, cu_seqlens, positions, slopes,
+                                      max_seqlen, H, scale, dqkv)
     torch.ops.dna_amd.linear_fwd(x, w, bias, y)                   y = x w^T (+ bias), bf16 MFMA
     torch.ops.dna_amd.geglu_fwd(g, p, seed, offset, a, fac)       a = dropout(gelu(g1) g2),
                                                                   fac = backward factors
@@ -104,6 +108,54 @@ def attn_bwd(qkv: torch.Tensor, out: torch.Tensor, dout: torch.Tensor, lse: torc
     N.call("dna_attn_bwd", qkv.data_ptr(), out.data_ptr(), dout.data_ptr(), lse.data_ptr(),
            _p(key_valid), slopes.data_ptr(), b, S, H, D, _DT[qkv.dtype], scale, dqkv.data_ptr(),
            delta.data_ptr(), N.stream_ptr())
+
+
+def _check_varlen(qkv, cu_seqlens, positions, slopes, max_seqlen, H):
+    _cuda_contig("qkv", qkv, (torch.bfloat16, torch.float32))
+    _check(qkv.dim() == 2 and qkv.shape[0] > 0 and qkv.shape[1] % (3 * H) == 0,
+           f"qkv must be [T, 3*H*D], got {tuple(qkv.shape)}")
+    _cuda_contig("cu_seqlens", cu_seqlens, (torch.int32,))
+    _check(cu_seqlens.dim() == 1 and cu_seqlens.numel() >= 2, "cu_seqlens must be [nseq + 1]")
+    if positions is not None:
+        _cuda_contig("positions", positions, (torch.int32,))
+        _check(positions.numel() == qkv.shape[0], "positions must hold T entries")
+    _cuda_contig("slopes", slopes, (torch.float32,))
+    _check(slopes.numel() == H, "slopes must hold H entries")
+    _check(max_seqlen > 0, "max_seqlen must be positive")
+    return qkv.shape[0], qkv.shape[1] // (3 * H), cu_seqlens.numel() - 1
+
+
+@torch.library.custom_op("dna_amd::attn_varlen_fwd", mutates_args=("out", "lse"))
+def attn_varlen_fwd(qkv: torch.Tensor, cu_seqlens: torch.Tensor, positions: torch.Tensor | None,
+                    slopes: torch.Tensor, max_seqlen: int, H: int, scale: float,
+                    out: torch.Tensor, lse: torch.Tensor) -> None:
+    """Packed ALiBi attention (csrc/attention_varlen.hip): rows cu_seqlens[n] .. cu_seqlens[n+1]-1
+    of qkv [T, 3*H*D] are sequence n; out [T, H*D], lse [H, T] fp32."""
+    T, D, nseq = _check_varlen(qkv, cu_seqlens, positions, slopes, max_seqlen, H)
+    _cuda_contig("out", out, (qkv.dtype,))
+    _check(tuple(out.shape) == (T, H * D), "out must be [T, H*D]")
+    _cuda_contig("lse", lse, (torch.float32,))
+    _check(lse.numel() == H * T, "lse must hold H*T floats")
+    N.call("dna_attn_varlen_fwd", qkv.data_ptr(), cu_seqlens.data_ptr(), _p(positions),
+           slopes.data_ptr(), nseq, T, max_seqlen, H, D, _DT[qkv.dtype], scale, out.data_ptr(),
+           lse.data_ptr(), N.stream_ptr())
+
+
+@torch.library.custom_op("dna_amd::attn_varlen_bwd", mutates_args=("dqkv",))
+def attn_varlen_bwd(qkv: torch.Tensor, out: torch.Tensor, dout: torch.Tensor, lse: torch.Tensor,
+                    cu_seqlens: torch.Tensor, positions: torch.Tensor | None, slopes: torch.Tensor,
+                    max_seqlen: int, H: int, scale: float, dqkv: torch.Tensor) -> None:
+    T, D, nseq = _check_varlen(qkv, cu_seqlens, positions, slopes, max_seqlen, H)
+    for n, t in (("out", out), ("dout", dout), ("dqkv", dqkv)):
+        _cuda_contig(n, t, (qkv.dtype,))
+    _cuda_contig("lse", lse, (torch.float32,))
+    _check(dqkv.shape == qkv.shape and dout.shape == out.shape and
+           tuple(out.shape) == (T, H * D) and lse.numel() == H * T, "dqkv / dout / out / lse shapes")
+    ws = torch.empty(N.lib().dna_attn_varlen_bwd_workspace(nseq, T, max_seqlen, H),
+                     device=qkv.device, dtype=torch.uint8)
+    N.call("dna_attn_varlen_bwd", qkv.data_ptr(), out.data_ptr(), dout.data_ptr(), lse.data_ptr(),
+           cu_seqlens.data_ptr(), _p(positions), slopes.data_ptr(), nseq, T, max_seqlen, H, D,
+           _DT[qkv.dtype], scale, dqkv.data_ptr(), ws.data_ptr(), N.stream_ptr())
 
 
 @torch.library.custom_op("dna_amd::alibi_attn_qkvpacked", mutates_args=())
@@ -715,8 +767,8 @@ def lm_head_rc_bwd(coef: torch.Tensor, h: torch.Tensor, w: torch.Tensor, cm: tor
            ws.data_ptr(), ws.numel() * 4, N.stream_ptr())
 
 
-OPS = ("attn_fwd", "attn_bwd", "alibi_attn_qkvpacked", "flash_attn_qkvpacked", "linear_fwd",
-       "transpose_bf16", "geglu_linear_fwd", "geglu_linear_dgrad",
+OPS = ("attn_fwd", "attn_bwd", "attn_varlen_fwd", "attn_varlen_bwd", "alibi_attn_qkvpacked",
+       "flash_attn_qkvpacked", "linear_fwd", "transpose_bf16", "geglu_linear_fwd", "geglu_linear_dgrad",
        "geglu_fwd", "geglu_bwd", "xent_fwd", "cls_head_fwd", "cls_loss", "cls_head_bwd", "pool_head_fwd",
        "pool_head_bwd", "pool_head_wide_fwd", "pool_head_wide_bwd", "lm_head_fwd", "lm_head_bwd",
        "lm_head_rc_fwd", "lm_head_rc_bwd")

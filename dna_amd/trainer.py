@@ -261,26 +261,32 @@ class _ClsSteps(ModuleTrainer):
         self.last_pred = None
 
     def _cls_loss(self, model, batch):
-        logits, loss, pred = model.cls_logits(*batch)
+        input_ids, labels, packed = batch
+        # the index goes on as a keyword only when there is one: a model without a packed path
+        # (SeqClsTrainer's) rejects the unknown argument itself
+        kw = {} if packed is None else {"packed": packed}
+        logits, loss, pred = model.cls_logits(input_ids, labels, **kw)
         self.last_logits, self.last_pred = logits.detach(), pred
         return loss
 
-    def step(self, input_ids, labels) -> torch.Tensor:
+    def step(self, input_ids, labels, packed=None) -> torch.Tensor:
         """One optimizer step on one batch (ids [b, S] and labels on the device: int64 [b] for a
         single-label head, fp32 [b, C] for a regression or multi-label one). The logits and
         (single-label; None otherwise) predictions of the step stay in last_logits / last_pred;
-        no host sync."""
-        return self._run([(input_ids, labels)], 1)
+        no host sync. packed: the batch's PackedIndex on the device (BertForSequenceClassification
+        only): the encoder runs on the real tokens instead of the padded rectangle."""
+        return self._run([(input_ids, labels, packed)], 1)
 
     @torch.no_grad()
-    def evaluate(self, input_ids, labels=None):
+    def evaluate(self, input_ids, labels=None, packed=None):
         """Eval-mode forward -> (logits, loss | None, pred | None); restores the training mode."""
         was = self.model.training
         self.model.eval()
         try:
             self._versions = _sync_shadow(self.flat, self._versions)
             with self._autocast():
-                return self.model.cls_logits(input_ids, labels)
+                kw = {} if packed is None else {"packed": packed}
+                return self.model.cls_logits(input_ids, labels, **kw)
         finally:
             self.model.train(was)
 

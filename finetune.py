@@ -4,6 +4,7 @@
     python finetune.py dataset.data_dir=/data/GUE/prom/prom_300_all \\
         train.pretrained_model_path=checkpoints/last.ckpt trainer.max_epochs=3
     python finetune.py --dry-run                       # compose + build, no GPU
+    python finetune.py dataset.unpad=true ...          # packed batches: no work on [PAD] rows
     python finetune.py experiment=hyena/genomic_benchmark_hyena dataset.dest_path=/data/gb
     python finetune.py experiment=caduceus/genomic_benchmark_caduceus dataset.dest_path=/data/gb
 
@@ -79,16 +80,21 @@ def _metric(problem_type, num_labels):
 
 @torch.no_grad()
 def evaluate(trainer, ds, batch_size, device, num_labels,
-             problem_type="single_label_classification"):
+             problem_type="single_label_classification", unpad=False):
     """-> {"loss", ...the problem type's metrics (_metric)} of one split; the metric's state
-    stays on the device until the split is done."""
+    stays on the device until the split is done. unpad: packed batches (dataset.unpad)."""
     metric, on_logits = _metric(problem_type, num_labels)
     total = torch.zeros((), device=device, dtype=torch.float64)
     for i in range(0, len(ds), batch_size):
         items = [ds[j] for j in range(i, min(i + batch_size, len(ds)))]
-        ids, labels = ds.collate(items)
+        if unpad:
+            ids, labels, packed = ds.collate(items, unpad=True)
+            packed = packed.to(device)
+        else:
+            (ids, labels), packed = ds.collate(items), None
         ids, labels = ids.to(device), labels.to(device)
-        logits, loss, pred = trainer.evaluate(ids, labels)
+        logits, loss, pred = (trainer.evaluate(ids, labels, packed=packed) if unpad
+                              else trainer.evaluate(ids, labels))
         total += loss.double() * len(items)
         metric.update(logits if on_logits else pred, labels)
     out = metric.compute()
@@ -206,6 +212,9 @@ def finetune_pool(cfg, dry_run=False, out=sys.stdout):
     if ds.get("_name_", "genomic_benchmark") not in POOL_DATASETS:
         raise ValueError(f"dataset._name_={ds.get('_name_')!r}: one of {POOL_DATASETS}")
     max_length = int(ds.get("max_length", 200))
+    if ds.get("unpad", False):
+        raise ValueError(f"dataset.unpad=true: model._name_={cfg.model._name_!r} has no packed "
+                         "path (fixed-length character tokens); dnabert2_cls only")
     tok = _char_tokenizer(max_length, ds.get("padding_side", "left"))
     if dry_run:
         model = _pool_model(cfg, int(ds.get("d_output") or 2), tok)
@@ -273,11 +282,14 @@ def finetune(cfg, dry_run=False, out=sys.stdout):
     data_dir = cfg.dataset.get("data_dir")
     if dry_run:
         model = BertForSequenceClassification(_model_config(cfg), precision=precision)
-        print(json.dumps({"dry_run": True, "model": cfg.model._name_,
-                          "model_params": sum(p.numel() for p in model.parameters()),
-                          "num_labels": model.num_labels, "data_dir": data_dir,
-                          "monitor": cfg.train.monitor, "mode": cfg.train.mode,
-                          "scheduler": sched, "optimizer": opt}), file=out)
+        info = {"dry_run": True, "model": cfg.model._name_,
+                "model_params": sum(p.numel() for p in model.parameters()),
+                "num_labels": model.num_labels, "data_dir": data_dir,
+                "monitor": cfg.train.monitor, "mode": cfg.train.mode,
+                "scheduler": sched, "optimizer": opt}
+        if cfg.dataset.get("unpad") is not None:  # dataset.unpad=true|false was given
+            info["unpad"] = bool(cfg.dataset.get("unpad"))
+        print(json.dumps(info), file=out)
         return None
     if not data_dir:
         raise ValueError("dataset.data_dir=<folder with train.csv, dev.csv, test.csv> is required")
@@ -317,6 +329,7 @@ def _fit(cfg, trainer, model, splits, device, out):
     ebs = int(cfg.dataset.get("eval_batch_size", bs))
     log_every = int(cfg.trainer.get("log_every_n_steps", 10))
     max_steps = cfg.train.get("max_steps")
+    unpad = bool(cfg.dataset.get("unpad", False))  # packed batches: no kernel runs on [PAD] rows
     gen = torch.Generator().manual_seed(int(cfg.train.get("seed") or 0))
     print(json.dumps({"event": "start", "train": len(train_ds), "dev": len(splits["dev"]),
                       "test": len(splits["test"]), "num_labels": model.num_labels,
@@ -326,9 +339,16 @@ def _fit(cfg, trainer, model, splits, device, out):
         order = (torch.randperm(len(train_ds), generator=gen) if cfg.dataset.get("shuffle", True)
                  else torch.arange(len(train_ds))).tolist()
         for i in range(0, len(order), bs):
-            ids, labels = train_ds.collate([train_ds[j] for j in order[i:i + bs]])
-            loss = trainer.step(ids.to(device, non_blocking=True),
-                                labels.to(device, non_blocking=True))
+            items = [train_ds[j] for j in order[i:i + bs]]
+            if unpad:
+                ids, labels, packed = train_ds.collate(items, unpad=True)
+                loss = trainer.step(ids.to(device, non_blocking=True),
+                                    labels.to(device, non_blocking=True),
+                                    packed=packed.to(device, non_blocking=True))
+            else:
+                ids, labels = train_ds.collate(items)
+                loss = trainer.step(ids.to(device, non_blocking=True),
+                                    labels.to(device, non_blocking=True))
             if trainer.global_step % log_every == 0:
                 print(json.dumps({"event": "train", "epoch": epoch, "step": trainer.global_step,
                                   "trainer/loss": loss.item(), "lr": trainer.opt.param_groups[0]["lr"]}),
@@ -339,7 +359,7 @@ def _fit(cfg, trainer, model, splits, device, out):
         for name, split in (("val", "dev"), ("test", "test")):
             for k, v in evaluate(trainer, splits[split], ebs, device, model.num_labels,
                                  getattr(model, "problem_type", None)
-                                 or "single_label_classification").items():
+                                 or "single_label_classification", unpad=unpad).items():
                 metrics[f"{name}/{k}"] = v
         print(json.dumps(dict({"event": "eval", "epoch": epoch, "step": trainer.global_step},
                               **metrics)), file=out, flush=True)

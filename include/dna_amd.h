@@ -24,8 +24,8 @@ extern "C" {
 
 #define DNA_AMD_ABI_VERSION 1
 /* Counts additions that leave every version-1 entry point as it was (a caller built against an
- * earlier revision keeps working): 1 = dna_lm_head_*, 2 = dna_lm_head_rc_*. */
-#define DNA_AMD_ABI_REVISION 2
+ * earlier revision keeps working): 1 = dna_lm_head_*, 2 = dna_lm_head_rc_*, 3 = dna_attn_varlen_*. */
+#define DNA_AMD_ABI_REVISION 3
 
 enum dna_status {
   DNA_OK = 0,
@@ -119,6 +119,39 @@ int dna_attn_bwd_var(const void* qkv, const void* out, const void* dout, const f
                      int head_dim, int dtype, float softmax_scale, void* dqkv, float* delta_ws,
                      float* dbias_part, int nw, void* stream);
 int dna_attn_dbias_part_rows(int batch, int seqlen);
+
+/* ------------------------------------------------------------------ packed (variable-length) ALiBi attention
+ * The same attention on an unpadded batch (csrc/attention_varlen.hip): the reference's layout
+ * between bert_padding.unpad_input and pad_input (bert_layers.py), where only the real tokens
+ * have rows. Sequence n owns rows cu_seqlens[n] .. cu_seqlens[n+1]-1 and a query attends to the
+ * keys of its own sequence only:
+ *   out_i = sum_j softmax_j(q_i . k_j * softmax_scale - slopes[h] * |pos_i - pos_j|) v_j
+ *
+ *   qkv        [total_rows, 3*heads*head_dim] (columns as in dna_attn_fwd), dtype
+ *   cu_seqlens [nseq + 1] int32, device memory, cu_seqlens[0] = 0, cu_seqlens[nseq] = total_rows;
+ *              lengths 1 .. max_seqlen, no alignment of any kind
+ *   positions  [total_rows] int32, the column of each token in the padded rectangle it came from
+ *              (so a [PAD] inside a row keeps the reference's |i - j|), or NULL: i - cu_seqlens[n]
+ *   out        [total_rows, heads*head_dim] dtype;  lse [heads, total_rows] fp32 (natural log)
+ * head_dim other than 64 is DNA_ERR_UNSUPPORTED; null pointers and non-positive sizes are
+ * DNA_ERR_INVALID; nothing is launched in either case. bf16 runs on MFMA with fp32 accumulation,
+ * fp32 is the exact parity path. Every global row index is clamped below total_rows before it
+ * becomes an address: a malformed cu_seqlens gives wrong numbers, never an out-of-bounds access. */
+int dna_attn_varlen_fwd(const void* qkv, const int* cu_seqlens, const int* positions,
+                        const float* slopes, int nseq, int total_rows, int max_seqlen, int heads,
+                        int head_dim, int dtype, float softmax_scale, void* out, float* lse,
+                        void* stream);
+/* Bytes of `workspace` for dna_attn_varlen_bwd (rowsum(dO*O), fp32 [heads, total_rows]); 0 for a
+ * non-positive size. */
+size_t dna_attn_varlen_bwd_workspace(int nseq, int total_rows, int max_seqlen, int heads);
+/* Backward of dna_attn_varlen_fwd: writes every element of dqkv [total_rows, 3*heads*head_dim]
+ * (dtype) when cu_seqlens covers all rows. dQ comes from a kernel over query tiles, dK and dV from
+ * one over key tiles, each recomputing the probabilities from lse: no atomics, the same call
+ * twice gives the same bits. The packed projection's bias gradient is not produced here. */
+int dna_attn_varlen_bwd(const void* qkv, const void* out, const void* dout, const float* lse,
+                        const int* cu_seqlens, const int* positions, const float* slopes, int nseq,
+                        int total_rows, int max_seqlen, int heads, int head_dim, int dtype,
+                        float softmax_scale, void* dqkv, void* workspace, void* stream);
 
 /* ------------------------------------------------------------------ fused (bias, act, dropout, residual) + LayerNorm
  * y = LN( dropout( act(x + bias) ) + residual ) over the last dim.
