@@ -16,7 +16,8 @@ LIB_PATH = os.environ.get("DNA_AMD_LIB", os.path.join(_HERE, "lib", "libdna_amd.
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "dna_amd.h")
 
 F32, BF16, F16 = 0, 1, 2
-ACT_NONE, ACT_GELU = 0, 1
+ACT_NONE, ACT_GELU, ACT_SIGMOID = 0, 1, 2
+DCONV_PLAIN, DCONV_GATE, DCONV_MAIN_MUL, DCONV_MAIN_ADD = 0, 1, 2, 3
 CLS_REGRESSION, CLS_SINGLE_LABEL, CLS_MULTI_LABEL = 0, 1, 2
 
 _vp, _i, _u64, _f, _sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_uint64, ctypes.c_float, ctypes.c_size_t
@@ -151,6 +152,16 @@ _SIGS = {
     "dna_lm_head_rc_bwd_workspace": (_sz, [_i, _i, _i]),
     "dna_lm_head_rc_bwd": (_i, [_vp, _vp, _i64, _i, _vp, _i, _vp, _vp, _vp, _vp, _f, _i, _i, _i,
                                 _vp, _i64, _vp, _i, _vp, _sz, _vp]),
+    "dna_dconv_fwd": (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp,
+                           _vp]),
+    "dna_dconv_bwd_elem": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _sz, _i, _vp, _vp, _vp]),
+    "dna_dconv_wgrad_splits": (_i, [_i, _i, _i, _i]),
+    "dna_dconv_wgrad_workspace": (_sz, [_i, _i, _i, _i]),
+    "dna_dconv_wgrad": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _sz, _vp]),
+    "dna_onehot_conv_fwd": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    "dna_onehot_conv_bwd_workspace": (_sz, [_i, _i, _i, _i, _i]),
+    "dna_onehot_conv_bwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp,
+                                 _sz, _vp]),
     "dna_sumsq_workspace": (_sz, [_sz]),
     "dna_sumsq": (_i, [_vp, _sz, _vp, _vp, _sz, _vp]),
     "dna_adamw_step": (_i, [_vp, _vp, _vp, _vp, _vp, _sz, _f, _f, _f, _f, _f, _i, _vp, _f, _f,

@@ -96,15 +96,35 @@ def string_reverse_complement(seq):
     return seq[::-1].translate(_COMPLEMENT)
 
 
+def remap_ids(ids):
+    """Character-tokenizer ids -> the one-hot models' alphabet (the reference's datasets with
+    use_tokenizer=False: genomic_bench_dataset.py:205-208, deepstarr.py:214-217,
+    deepsea.py:188-191, hg38_dataset.py:383-386): ids - 7, then everything >= 4 or < 0 becomes 4.
+    With the character vocabulary A C G T N = 7..11 that is A C G T = 0..3 and N, padding and
+    every special token = 4."""
+    ids = ids - 7
+    return torch.where((ids >= 4) | (ids < 0), torch.full_like(ids, 4), ids)
+
+
+def _want_remap(use_tokenizer, id_remap):
+    """Both spellings of the remap: use_tokenizer=False (the reference's) or id_remap=True."""
+    return (not use_tokenizer) if id_remap is None else bool(id_remap)
+
+
 class _CharItems(torch.utils.data.Dataset):
     """What the character-level fine-tuning datasets share: how a sequence becomes an item.
     Tokenisation as the reference calls its tokenizer: truncation to max_length, padding to
     max_length on the tokenizer's side (left by default), add_eos appends [SEP] inside max_length,
     rc_aug replaces a sequence by its reverse complement with probability 1/2 per access (`rng`:
     a random.Random, for seeded draws). Items are (ids int64 [max_length], target) and, with
-    return_mask, the attention mask (bool [max_length], False on padding) as a third entry."""
+    return_mask, the attention mask (bool [max_length], False on padding) as a third entry.
+    id_remap (the reference's use_tokenizer=False, for its one-hot models such as denoise_cnn):
+    the ids become `remap_ids` of the tokenizer's -- A C G T = 0..3 and everything else, padding
+    included, 4 -- and the mask is taken from the tokenizer's ids before that."""
 
-    def _init_items(self, max_length, tokenizer, use_padding, add_eos, rc_aug, return_mask, rng):
+    def _init_items(self, max_length, tokenizer, use_padding, add_eos, rc_aug, return_mask, rng,
+                    id_remap=False):
+        self.id_remap = bool(id_remap)
         self.max_length = int(max_length)
         self.tokenizer = tokenizer or CharacterTokenizer(["A", "C", "G", "T", "N"],
                                                          self.max_length + 2)
@@ -123,8 +143,11 @@ class _CharItems(torch.utils.data.Dataset):
                              padding="max_length" if self.use_padding else False,
                              max_length=self.max_length, truncation=True)["input_ids"]
         ids = torch.tensor(ids, dtype=torch.int64)
+        mask = ids != self.pad_token_id
+        if self.id_remap:
+            ids = remap_ids(ids)
         if self.return_mask:
-            return ids, target, ids != self.pad_token_id
+            return ids, target, mask
         return ids, target
 
     def collate(self, items):
@@ -149,18 +172,20 @@ class GenomicBenchmarkFolder(_CharItems):
     by default), add_eos appends [SEP] inside max_length, rc_aug replaces a sequence by its
     reverse complement with probability 1/2 per access (`rng`: a random.Random, for seeded
     draws). classes: the class folders another split of the dataset has (its `.classes`); a
-    split whose folders differ is an error, since a missing class would shift the labels."""
+    split whose folders differ is an error, since a missing class would shift the labels.
+    use_tokenizer=False (or id_remap=True): the ids of the one-hot models (`remap_ids`)."""
 
     def __init__(self, dest_path, dataset_name, split, max_length, tokenizer=None, d_output=None,
                  use_padding=True, add_eos=False, rc_aug=False, return_mask=False, rng=None,
-                 classes=None):
+                 classes=None, use_tokenizer=True, id_remap=None):
         self.split = "test" if split == "val" else split
         self.base_path = os.path.join(str(dest_path), dataset_name, self.split)
         if not os.path.isdir(self.base_path):
             raise FileNotFoundError(
                 f"{self.base_path}: no such folder. Genomic Benchmarks data is not downloaded "
                 f"here; put the dataset at <dest_path>/{dataset_name}/{self.split}/<class>/*.txt")
-        self._init_items(max_length, tokenizer, use_padding, add_eos, rc_aug, return_mask, rng)
+        self._init_items(max_length, tokenizer, use_padding, add_eos, rc_aug, return_mask, rng,
+                         _want_remap(use_tokenizer, id_remap))
         self.classes = sorted(d for d in os.listdir(self.base_path)
                               if os.path.isdir(os.path.join(self.base_path, d)))
         if not self.classes:
@@ -200,16 +225,18 @@ class DeepSTARRFolder(_CharItems):
     count differs from the table's.
 
     Items are (ids int64 [max_length], target fp32 [2]) (+ mask); tokenisation, add_eos, rc_aug,
-    return_mask and collate as in _CharItems. use_tokenizer=False (the reference's id remap for
-    its diffusion models) is not built."""
+    return_mask and collate as in _CharItems. id_remap=True gives the ids of the one-hot models
+    (`remap_ids`, the reference's use_tokenizer=False). The spelling use_tokenizer=False itself
+    stays the error it has always been here (callers rely on it): it names id_remap."""
 
     num_labels = d_output = len(DEEPSTARR_TARGETS)
 
     def __init__(self, dest_path, split, max_length, tokenizer=None, use_padding=True,
-                 add_eos=False, rc_aug=False, return_mask=False, rng=None, use_tokenizer=True):
+                 add_eos=False, rc_aug=False, return_mask=False, rng=None, use_tokenizer=True,
+                 id_remap=False):
         if not use_tokenizer:
-            raise NotImplementedError("DeepSTARRFolder use_tokenizer=False (the diffusion models' "
-                                      "id remap) is not built")
+            raise NotImplementedError("DeepSTARRFolder use_tokenizer=False is not taken: the "
+                                      "diffusion models' id remap is id_remap=True here")
         if split.lower() not in _DEEPSTARR_SPLITS:
             raise ValueError(f"split {split!r}: one of {sorted(_DEEPSTARR_SPLITS)}")
         name = _DEEPSTARR_SPLITS[split.lower()]
@@ -220,7 +247,8 @@ class DeepSTARRFolder(_CharItems):
                 raise FileNotFoundError(
                     f"{path}: no such file. DeepSTARR data is not downloaded here; put "
                     f"Sequences_{name}.fa and Sequences_activity_{name}.txt into <dest_path>")
-        self._init_items(max_length, tokenizer, use_padding, add_eos, rc_aug, return_mask, rng)
+        self._init_items(max_length, tokenizer, use_padding, add_eos, rc_aug, return_mask, rng,
+                         id_remap)
         with open(self.table_path, newline="") as f:
             rows = csv.reader(f, delimiter="\t")
             header = next(rows, [])
@@ -267,16 +295,14 @@ class DeepSEACsv(_CharItems):
     that says where it is expected.
 
     Items are (ids int64 [max_length], target fp32 [919]) (+ mask); tokenisation, add_eos, rc_aug,
-    return_mask and collate as in _CharItems."""
+    return_mask and collate as in _CharItems. use_tokenizer=False (or id_remap=True): the ids of
+    the one-hot models (`remap_ids`)."""
 
     num_labels = d_output = DEEPSEA_LABELS
 
     def __init__(self, dest_path, split, max_length, max_rows=40000, tokenizer=None,
                  use_padding=True, add_eos=False, rc_aug=False, return_mask=False, rng=None,
-                 use_tokenizer=True):
-        if not use_tokenizer:
-            raise NotImplementedError("DeepSEACsv use_tokenizer=False (the diffusion models' id "
-                                      "remap) is not built")
+                 use_tokenizer=True, id_remap=None):
         split = "valid" if split.lower() == "val" else split.lower()
         if split not in ("train", "valid", "test"):
             raise ValueError(f"split {split!r}: one of train, val / valid, test")
@@ -285,7 +311,8 @@ class DeepSEACsv(_CharItems):
             raise FileNotFoundError(
                 f"{self.path}: no such file. DeepSEA data is not downloaded here; put train.csv.gz, "
                 "valid.csv.gz and test.csv.gz into <dest_path>")
-        self._init_items(max_length, tokenizer, use_padding, add_eos, rc_aug, return_mask, rng)
+        self._init_items(max_length, tokenizer, use_padding, add_eos, rc_aug, return_mask, rng,
+                         _want_remap(use_tokenizer, id_remap))
         self.all_seqs, rows = [], []
         with gzip.open(self.path, "rt", newline="") as f:
             for i, row in enumerate(csv.reader(f)):

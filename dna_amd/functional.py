@@ -1837,3 +1837,178 @@ def linear(x, w, w_lp, b=None, w_lpt=None, geglu=None):
     """geglu=(p, seed, offset): the output feeds GeGLU.apply(y, p, seed, offset) next -- fuse
     that GeGLU forward into the GEMM epilogue when the shapes allow (DNA_GEGLU_FUSED=0: never)."""
     return Linear.apply(x, w, w_lp if w_lp is not None else w, b, w_lpt, geglu)
+
+
+# ----------------------------------------------------------------------------------- dilated conv
+def conv_impl():
+    """"hip" (default): the dilated convolutions on csrc/dilated_conv.hip; "torch": F.conv1d
+    (MIOpen), for measurement only (DNA_CONV_IMPL; counted as a library fallback, so
+    DNA_STRICT_NATIVE=1 refuses it)."""
+    return os.environ.get("DNA_CONV_IMPL", "hip")
+
+
+def _shadow(w, dt):
+    """The parameter in the compute dtype: the trainer's persistent bf16 copy (`_dna_lp`) while it
+    still stands for the parameter -- the trainer stamps the parameter's version on it whenever it
+    re-derives the copy, and an in-place change outside the fused AdamW step (load_state_dict, a
+    manual edit) moves the version on -- else a cast of the parameter itself."""
+    lp = getattr(w, "_dna_lp", None)
+    if (dt == torch.bfloat16 and lp is not None
+            and getattr(w, "_dna_lp_version", None) == w._version):
+        return lp
+    return w.detach().to(dt)
+
+
+def conv_taps(w, dt):
+    """Conv1d weight [co, ci, K] -> the kernel's tap-major [K, co, ci] in the compute dtype."""
+    return _shadow(w, dt).permute(2, 0, 1).contiguous()
+
+
+def conv_taps_dgrad(w, dt):
+    """The data gradient's weight: taps reversed, W transposed -> [K, ci, co]."""
+    return _shadow(w, dt).flip(2).permute(2, 1, 0).contiguous()
+
+
+def _dconv(x, w_taps, bias, dilation, epilogue, act, g=None, res=None, out=None, z=None,
+           res_out=None):
+    B, L, C = x.shape
+    K = w_taps.shape[0]
+    with _timed("dconv", 2.0 * B * L * C * C * K):
+        N.call("dna_dconv_fwd", x.data_ptr(), _dt(x), w_taps.data_ptr(), _p(bias), B, L, C, K,
+               int(dilation), epilogue, act, _p(g), _p(res), _p(out), _p(z), _p(res_out),
+               N.stream_ptr())
+
+
+def _dconv_wgrad(dz, x, w, b, dilation):
+    """(dW, db) of one Conv1d(C, C, K), or (None, None) after adding them straight into the flat
+    gradient when a FlatParams trainer owns both parameters."""
+    B, L, C = x.shape
+    K = w.shape[2]
+    direct = _param_grads_direct((w, b)) and tuple(w.grad.shape) == tuple(w.shape)
+    dw = w.grad if direct else torch.empty(C, C, K, device=x.device, dtype=torch.float32)
+    db = None if b is None else (b.grad if direct else torch.empty(C, device=x.device,
+                                                                   dtype=torch.float32))
+    nws = N.lib().dna_dconv_wgrad_workspace(B, L, C, K)
+    ws = torch.empty(nws, device=x.device, dtype=torch.uint8)
+    with _timed("dconv_wgrad", 2.0 * B * L * C * C * K):
+        N.call("dna_dconv_wgrad", dz.data_ptr(), x.data_ptr(), _dt(x), B, L, C, K, int(dilation),
+               dw.data_ptr(), _p(db), int(direct), ws.data_ptr(), nws, N.stream_ptr())
+    if direct:
+        _notify_direct(w, b)
+        return None, None
+    return dw, db
+
+
+class GatedDilatedConv(torch.autograd.Function):
+    """One layer of the reference's CNNModel in mode "dilation" (denoise.py:469-484) after its two
+    LayerNorms, as one node:
+        g = act_g(gates[i](rc_norm)),  h = gelu(convs[i](h_norm))       act_g: sigmoid | gelu
+        feat_new = h * g + feat (forget) | h + g + feat,   rc_new = g + rc
+    h_norm, rc_norm [B, L, C] channels-last in the compute dtype (bf16 under bf16 autocast, else
+    fp32); feat, rc, feat_new, rc_new fp32 (the residual streams stay fp32). Two launches of
+    dna_dconv_fwd, the combine in their epilogues; saved for the backward: the two inputs, z_h,
+    g and (GELU gate) z_g. Backward: one elementwise kernel (dz_h, dz_g), the two data gradients
+    through the same convolution kernel, the weight and bias gradients from split partials
+    (deterministic), written straight into the flat gradient where a trainer owns the parameters."""
+
+    @staticmethod
+    def forward(ctx, h_norm, rc_norm, feat, rc, conv_w, conv_b, gate_w, gate_b, dilation, forget):
+        _gpu(h_norm, rc_norm, feat, rc, conv_w, gate_w)
+        B, L, C = h_norm.shape
+        # every conv of this model maps C to C, so h always has feat's shape (the reference's
+        # `else: feat = h` branch cannot be reached)
+        assert conv_w.shape[:2] == (C, C) and gate_w.shape == conv_w.shape, \
+            "GatedDilatedConv: Conv1d(C, C, K) only"
+        assert rc_norm.shape == h_norm.shape == feat.shape == rc.shape
+        dt = h_norm.dtype
+        x_h, x_g = h_norm.contiguous(), rc_norm.to(dt).contiguous()
+        feat, rc = feat.float().contiguous(), rc.float().contiguous()
+        forget = bool(forget)
+        g = torch.empty_like(x_g)
+        z_g = None if forget else torch.empty_like(x_g)
+        rc_new, feat_new = torch.empty_like(rc), torch.empty_like(feat)
+        z_h = torch.empty_like(x_h)
+        _dconv(x_g, conv_taps(gate_w, dt), gate_b, dilation, N.DCONV_GATE,
+               N.ACT_SIGMOID if forget else N.ACT_GELU, res=rc, out=g, z=z_g, res_out=rc_new)
+        _dconv(x_h, conv_taps(conv_w, dt), conv_b, dilation,
+               N.DCONV_MAIN_MUL if forget else N.DCONV_MAIN_ADD, N.ACT_GELU, g=g, res=feat, z=z_h,
+               res_out=feat_new)
+        ctx.save_for_backward(x_h, x_g, z_h, g, z_g)
+        ctx.params = (conv_w, conv_b, gate_w, gate_b)
+        ctx.cfg = (int(dilation), forget)
+        ctx.set_materialize_grads(False)
+        return feat_new, rc_new
+
+    @staticmethod
+    def backward(ctx, dfeat, drc):
+        x_h, x_g, z_h, g, z_g = ctx.saved_tensors
+        conv_w, conv_b, gate_w, gate_b = ctx.params
+        dilation, forget = ctx.cfg
+        if dfeat is None:
+            dfeat = torch.zeros(x_h.shape, device=x_h.device, dtype=torch.float32)
+        dfeat = dfeat.float().contiguous()
+        drc = None if drc is None else drc.float().contiguous()
+        dz_h, dz_g = torch.empty_like(z_h), torch.empty_like(z_h)
+        N.call("dna_dconv_bwd_elem", dfeat.data_ptr(), _p(drc), z_h.data_ptr(), g.data_ptr(),
+               _p(z_g), _dt(z_h), z_h.numel(), int(forget), dz_h.data_ptr(), dz_g.data_ptr(),
+               N.stream_ptr())
+        dt = x_h.dtype
+        dx_h = dx_g = None
+        if ctx.needs_input_grad[0]:
+            dx_h = torch.empty_like(x_h)
+            _dconv(dz_h, conv_taps_dgrad(conv_w, dt), None, dilation, N.DCONV_PLAIN, N.ACT_NONE,
+                   out=dx_h)
+        if ctx.needs_input_grad[1]:
+            dx_g = torch.empty_like(x_g)
+            _dconv(dz_g, conv_taps_dgrad(gate_w, dt), None, dilation, N.DCONV_PLAIN, N.ACT_NONE,
+                   out=dx_g)
+        dwc, dbc = _dconv_wgrad(dz_h, x_h, conv_w, conv_b, dilation)
+        dwg, dbg = _dconv_wgrad(dz_g, x_g, gate_w, gate_b, dilation)
+        return dx_h, dx_g, dfeat, drc, dwc, dbc, dwg, dbg, None, None
+
+
+class OneHotConv(torch.autograd.Function):
+    """gelu(Conv1d(V, C, KW, padding (KW - 1) / 2)(one_hot(ids))) -> [B, L, C] fp32 as a table
+    lookup (dna_onehot_conv_fwd); complement: on 3 - id for id < 4 (N stays). The backward
+    recomputes z and sums the [C, V, KW] gradient from per-block partials in a fixed order."""
+
+    @staticmethod
+    def forward(ctx, ids, w, b, complement):
+        _gpu(ids, w, b)
+        ids = ids.to(torch.int64).contiguous()
+        B, L = ids.shape
+        C, V, KW = w.shape
+        w32, b32 = w.detach().float().contiguous(), None if b is None else b.detach().float().contiguous()
+        out = torch.empty(B, L, C, device=ids.device, dtype=torch.float32)
+        N.call("dna_onehot_conv_fwd", ids.data_ptr(), w32.data_ptr(), _p(b32), B, L, C, V, KW,
+               int(bool(complement)), N.ACT_GELU, out.data_ptr(), N.stream_ptr())
+        ctx.save_for_backward(ids)
+        ctx.params = (w, b)
+        ctx.complement = bool(complement)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        (ids,) = ctx.saved_tensors
+        w, b = ctx.params
+        B, L = ids.shape
+        C, V, KW = w.shape
+        dout = dout.float().contiguous()
+        direct = _param_grads_direct((w, b)) and tuple(w.grad.shape) == tuple(w.shape)
+        dw = w.grad if direct else torch.empty(C, V, KW, device=ids.device, dtype=torch.float32)
+        db = None if b is None else (b.grad if direct else torch.empty(C, device=ids.device,
+                                                                       dtype=torch.float32))
+        w32, b32 = w.detach().float().contiguous(), None if b is None else b.detach().float().contiguous()
+        nws = N.lib().dna_onehot_conv_bwd_workspace(B, L, C, V, KW)
+        ws = torch.empty(nws, device=ids.device, dtype=torch.uint8)
+        N.call("dna_onehot_conv_bwd", ids.data_ptr(), w32.data_ptr(), _p(b32), dout.data_ptr(), B,
+               L, C, V, KW, int(ctx.complement), N.ACT_GELU, dw.data_ptr(), _p(db), int(direct),
+               ws.data_ptr(), nws, N.stream_ptr())
+        if direct:
+            _notify_direct(w, b)
+            return None, None, None, None
+        return None, dw, db, None
+
+
+def onehot_conv(ids, weight, bias, complement=False):
+    return OneHotConv.apply(ids, weight, bias, complement)

@@ -33,6 +33,13 @@ asserts (flash_attn_triton.py:849-855) -- instead of letting a kernel read out o
     torch.ops.dna_amd.lm_head_rc_fwd(h, w, cm, labels, denom, loss, count, coef)   h [T, 2 D]
     torch.ops.dna_amd.lm_head_rc_bwd(coef, h, w, cm, labels, count, upstream, denom, dh, dw,
                                      accumulate)
+    torch.ops.dna_amd.dconv_fwd(x, w_taps, bias, dilation, epilogue, act, g, res, out, z_out,
+                                res_out)                          dilated Conv1d + gated epilogues
+    torch.ops.dna_amd.dconv_bwd_elem(dfeat, drc, z_h, g, z_g, forget, dz_h, dz_g)
+    torch.ops.dna_amd.dconv_wgrad(dz, x, dilation, dw, dbias, accumulate)
+    torch.ops.dna_amd.onehot_conv_fwd(input_ids, w, bias, complement, act, out)
+    torch.ops.dna_amd.onehot_conv_bwd(input_ids, w, bias, dout, complement, act, dw, dbias,
+                                      accumulate)
 and the reference's FlashAttention kernel slot with its own signature (flash_attn_triton.py:
 1077-1130, called at bert_layers.py:188/192 as flash_attn_qkvpacked_func(qkv, bias)), autograd
 included:
@@ -767,8 +774,133 @@ def lm_head_rc_bwd(coef: torch.Tensor, h: torch.Tensor, w: torch.Tensor, cm: tor
            ws.data_ptr(), ws.numel() * 4, N.stream_ptr())
 
 
+# ------------------------------------------------------------------------------- dilated conv
+_DCONV_EPI = {"plain": N.DCONV_PLAIN, "gate": N.DCONV_GATE, "main_mul": N.DCONV_MAIN_MUL,
+              "main_add": N.DCONV_MAIN_ADD}
+_DCONV_ACT = {"none": N.ACT_NONE, "gelu": N.ACT_GELU, "sigmoid": N.ACT_SIGMOID}
+
+
+def _dconv_x(name, t, like=None):
+    _cuda_contig(name, t, (torch.bfloat16, torch.float32))
+    _check(t.dim() == 3, f"{name} must be [B, L, C], got {tuple(t.shape)}")
+    if like is not None:
+        _check(t.shape == like.shape and t.dtype == like.dtype, f"{name} must match x")
+    return t.shape
+
+
+def _dconv_res(name, t, x):
+    _cuda_contig(name, t, (torch.float32,))
+    _check(t.shape == x.shape, f"{name} must be fp32 {tuple(x.shape)}")
+
+
+@torch.library.custom_op("dna_amd::dconv_fwd", mutates_args=("out", "z_out", "res_out"))
+def dconv_fwd(x: torch.Tensor, w_taps: torch.Tensor, bias: torch.Tensor | None, dilation: int,
+              epilogue: str, act: str, g: torch.Tensor | None, res: torch.Tensor | None,
+              out: torch.Tensor | None, z_out: torch.Tensor | None,
+              res_out: torch.Tensor | None) -> None:
+    """The dilated convolution of x [B, L, C] with the tap-major weight w_taps [K, C, C] and one
+    of the epilogues plain | gate | main_mul | main_add (dna_dconv_fwd, include/dna_amd.h)."""
+    B, L, C = _dconv_x("x", x)
+    _cuda_contig("w_taps", w_taps, (x.dtype,))
+    _check(w_taps.dim() == 3 and tuple(w_taps.shape[1:]) == (C, C),
+           f"w_taps must be [K, {C}, {C}] in x's dtype, got {tuple(w_taps.shape)}")
+    _check(epilogue in _DCONV_EPI and act in _DCONV_ACT, f"epilogue {epilogue!r} / act {act!r}")
+    if bias is not None:
+        _cuda_contig("bias", bias, (torch.float32,))
+        _check(bias.numel() == C, "bias must hold C floats")
+    for n, t in (("g", g), ("out", out), ("z_out", z_out)):
+        if t is not None:
+            _dconv_x(n, t, x)
+    for n, t in (("res", res), ("res_out", res_out)):
+        if t is not None:
+            _dconv_res(n, t, x)
+    N.call("dna_dconv_fwd", x.data_ptr(), _DT[x.dtype], w_taps.data_ptr(), _p(bias), B, L, C,
+           w_taps.shape[0], int(dilation), _DCONV_EPI[epilogue], _DCONV_ACT[act], _p(g), _p(res),
+           _p(out), _p(z_out), _p(res_out), N.stream_ptr())
+
+
+@torch.library.custom_op("dna_amd::dconv_bwd_elem", mutates_args=("dz_h", "dz_g"))
+def dconv_bwd_elem(dfeat: torch.Tensor, drc: torch.Tensor | None, z_h: torch.Tensor,
+                   g: torch.Tensor | None, z_g: torch.Tensor | None, forget: bool,
+                   dz_h: torch.Tensor, dz_g: torch.Tensor) -> None:
+    """dz_h, dz_g of one gated layer from the gradients of its two new residual streams."""
+    _dconv_x("z_h", z_h)
+    _dconv_res("dfeat", dfeat, z_h)
+    if drc is not None:
+        _dconv_res("drc", drc, z_h)
+    for n, t in (("g", g), ("z_g", z_g), ("dz_h", dz_h), ("dz_g", dz_g)):
+        if t is not None:
+            _dconv_x(n, t, z_h)
+    _check((g if forget else z_g) is not None, "forget needs g, otherwise z_g")
+    N.call("dna_dconv_bwd_elem", dfeat.data_ptr(), _p(drc), z_h.data_ptr(), _p(g), _p(z_g),
+           _DT[z_h.dtype], z_h.numel(), int(forget), dz_h.data_ptr(), dz_g.data_ptr(),
+           N.stream_ptr())
+
+
+@torch.library.custom_op("dna_amd::dconv_wgrad", mutates_args=("dw", "dbias"))
+def dconv_wgrad(dz: torch.Tensor, x: torch.Tensor, dilation: int, dw: torch.Tensor,
+                dbias: torch.Tensor | None, accumulate: bool) -> None:
+    """dw [C, C, K] (+)= the weight gradient, dbias [C] (+)= sum dz, both fp32, deterministic."""
+    B, L, C = _dconv_x("x", x)
+    _dconv_x("dz", dz, x)
+    _cuda_contig("dw", dw, (torch.float32,))
+    _check(dw.dim() == 3 and tuple(dw.shape[:2]) == (C, C), f"dw must be [{C}, {C}, K]")
+    if dbias is not None:
+        _cuda_contig("dbias", dbias, (torch.float32,))
+        _check(dbias.numel() == C, "dbias must hold C floats")
+    K = dw.shape[2]
+    nws = N.lib().dna_dconv_wgrad_workspace(B, L, C, K)
+    ws = torch.empty(max(nws, 16) // 4, device=x.device, dtype=torch.float32)
+    N.call("dna_dconv_wgrad", dz.data_ptr(), x.data_ptr(), _DT[x.dtype], B, L, C, K, int(dilation),
+           dw.data_ptr(), _p(dbias), int(accumulate), ws.data_ptr(), ws.numel() * 4,
+           N.stream_ptr())
+
+
+def _onehot_args(ids, w, bias):
+    _cuda_contig("input_ids", ids, (torch.int64,))
+    _check(ids.dim() == 2, "input_ids must be [B, L]")
+    _cuda_contig("w", w, (torch.float32,))
+    _check(w.dim() == 3, "w must be [C, V, KW]")
+    if bias is not None:
+        _cuda_contig("bias", bias, (torch.float32,))
+        _check(bias.numel() == w.shape[0], "bias must hold C floats")
+    return ids.shape[0], ids.shape[1], w.shape[0], w.shape[1], w.shape[2]
+
+
+@torch.library.custom_op("dna_amd::onehot_conv_fwd", mutates_args=("out",))
+def onehot_conv_fwd(input_ids: torch.Tensor, w: torch.Tensor, bias: torch.Tensor | None,
+                    complement: bool, act: str, out: torch.Tensor) -> None:
+    """out [B, L, C] fp32 = act(Conv1d(V, C, KW)(one_hot(ids))) as a table lookup."""
+    B, L, C, V, KW = _onehot_args(input_ids, w, bias)
+    _cuda_contig("out", out, (torch.float32,))
+    _check(tuple(out.shape) == (B, L, C), f"out must be {(B, L, C)}")
+    N.call("dna_onehot_conv_fwd", input_ids.data_ptr(), w.data_ptr(), _p(bias), B, L, C, V, KW,
+           int(complement), _DCONV_ACT[act], out.data_ptr(), N.stream_ptr())
+
+
+@torch.library.custom_op("dna_amd::onehot_conv_bwd", mutates_args=("dw", "dbias"))
+def onehot_conv_bwd(input_ids: torch.Tensor, w: torch.Tensor, bias: torch.Tensor | None,
+                    dout: torch.Tensor, complement: bool, act: str, dw: torch.Tensor,
+                    dbias: torch.Tensor | None, accumulate: bool) -> None:
+    """dw [C, V, KW] and dbias [C] (+)= the gradients of onehot_conv_fwd, deterministic."""
+    B, L, C, V, KW = _onehot_args(input_ids, w, bias)
+    _cuda_contig("dout", dout, (torch.float32,))
+    _check(tuple(dout.shape) == (B, L, C), f"dout must be {(B, L, C)}")
+    _cuda_contig("dw", dw, (torch.float32,))
+    _check(dw.shape == w.shape, "dw must match w")
+    if dbias is not None:
+        _cuda_contig("dbias", dbias, (torch.float32,))
+        _check(dbias.numel() == C, "dbias must hold C floats")
+    nws = N.lib().dna_onehot_conv_bwd_workspace(B, L, C, V, KW)
+    ws = torch.empty(max(nws, 16) // 4, device=dout.device, dtype=torch.float32)
+    N.call("dna_onehot_conv_bwd", input_ids.data_ptr(), w.data_ptr(), _p(bias), dout.data_ptr(),
+           B, L, C, V, KW, int(complement), _DCONV_ACT[act], dw.data_ptr(), _p(dbias),
+           int(accumulate), ws.data_ptr(), ws.numel() * 4, N.stream_ptr())
+
+
 OPS = ("attn_fwd", "attn_bwd", "attn_varlen_fwd", "attn_varlen_bwd", "alibi_attn_qkvpacked",
        "flash_attn_qkvpacked", "linear_fwd", "transpose_bf16", "geglu_linear_fwd", "geglu_linear_dgrad",
        "geglu_fwd", "geglu_bwd", "xent_fwd", "cls_head_fwd", "cls_loss", "cls_head_bwd", "pool_head_fwd",
        "pool_head_bwd", "pool_head_wide_fwd", "pool_head_wide_bwd", "lm_head_fwd", "lm_head_bwd",
-       "lm_head_rc_fwd", "lm_head_rc_bwd")
+       "lm_head_rc_fwd", "lm_head_rc_bwd", "dconv_fwd", "dconv_bwd_elem", "dconv_wgrad",
+       "onehot_conv_fwd", "onehot_conv_bwd")

@@ -56,6 +56,10 @@ def _sync_shadow(flat, versions):
     v = [p._version for p in flat.params]
     if v != versions:
         flat.refresh_shadow()
+        # the version the copy stands for: a reader outside the trainer (functional._shadow) takes
+        # the copy only while the parameter still has it, and casts the parameter otherwise
+        for p, pv in zip(flat.params, v):
+            p._dna_lp_version = pv
     return v
 
 

@@ -18,7 +18,8 @@ written by train.py (the MLM head is dropped, pooler and classifier start from t
 initialisation) or a fine-tuning checkpoint.
 
 model._name_ picks the path: dnabert2_cls as above; dna_embedding (HyenaDNA backbone +
-SequenceDecoder) and caduceus_cls (CaduceusForSequenceClassification) read a Genomic Benchmarks
+SequenceDecoder), caduceus_cls (CaduceusForSequenceClassification) and denoise_cnn (the gated
+dilated-CNN backbone + SequenceDecoder, experiment=denoise/*, dataset.use_tokenizer=false) read a Genomic Benchmarks
 folder (dataset.dest_path / dataset.dataset_name, character tokens at a fixed length), train with
 SeqClsTrainer on the fused pooling head, and share the epoch loop, metrics, events and
 checkpoints. The benchmarks have no validation split: val and test are both the test folder.
@@ -102,7 +103,7 @@ def evaluate(trainer, ds, batch_size, device, num_labels,
     return out
 
 
-POOL_MODELS = ("dna_embedding", "caduceus_cls")
+POOL_MODELS = ("dna_embedding", "caduceus_cls", "denoise_cnn")
 
 
 def _char_tokenizer(max_length, padding_side="left"):
@@ -137,6 +138,16 @@ def _pool_model(cfg, num_labels, tokenizer):
         return SequenceClassifier(DNAEmbeddingModel(**mc), num_labels, mode=dec.get("mode", "pool"),
                                   use_lengths=dec.get("use_lengths", False), problem_type=problem,
                                   loss_scale=scale)
+    if cfg.model._name_ == "denoise_cnn":
+        from dna_amd.decoders import SequenceClassifier
+        from dna_amd.denoise import CNNModel
+        dec = cfg.get("decoder")
+        dec = dec.to_container() if dec is not None else {}
+        if dec.get("_name_", "sequence") != "sequence":
+            raise NotImplementedError(f"decoder {dec.get('_name_')!r} (sequence only)")
+        return SequenceClassifier(CNNModel(**mc), num_labels, mode=dec.get("mode", "pool"),
+                                  use_lengths=dec.get("use_lengths", False), problem_type=problem,
+                                  loss_scale=scale)
     from dna_amd.caduceus import CaduceusForSequenceClassification
     head = {k: mc.pop(k) for k in ("pooling_strategy", "conjoin_train", "conjoin_eval") if k in mc}
     config = mc.pop("config")
@@ -158,6 +169,18 @@ def load_pretrained(model, state_dict, freeze_backbone=False):
     from dna_amd.decoders import SequenceClassifier
     from dna_amd.trainer import strip_model_prefix
     sd = strip_model_prefix(state_dict)
+    from dna_amd.denoise import CNNModel
+    if isinstance(model, SequenceClassifier) and isinstance(model.model, CNNModel):
+        # denoise_cnn: one of this script's checkpoints (keys model.* and decoder.0.*: everything,
+        # strictly) or a same-key backbone state dict (the reference's; its decoder.* keys are
+        # dropped and the head stays fresh), also strictly
+        if freeze_backbone:
+            raise NotImplementedError("freeze_backbone is built for dna_embedding only")
+        if any(k.startswith("model.") for k in sd):
+            model.load_state_dict(sd)
+            return {"loaded": "classifier"}
+        model.model.load_state_dict({k: v for k, v in sd.items() if not k.startswith("decoder.")})
+        return {"loaded": "backbone", "kept_fresh": ["decoder.0.output_transform"]}
     if isinstance(model, SequenceClassifier):
         if any(k.startswith("decoder.0.") for k in sd):
             model.load_state_dict(sd)
@@ -178,8 +201,9 @@ def _pool_splits(ds, tok, max_length):
     split (dev is the test folder); DeepSTARR and DeepSEA have their own train / val / test
     files."""
     from dna_amd import finetune_data as FD
+    # dataset.use_tokenizer=false (the one-hot models): ids A C G T N = 0..4 (finetune_data.remap_ids)
     kw = dict(max_length=max_length, tokenizer=tok, use_padding=ds.get("use_padding", True),
-              add_eos=ds.get("add_eos", False))
+              add_eos=ds.get("add_eos", False), id_remap=not ds.get("use_tokenizer", True))
     rc = ds.get("rc_aug", False)
     name = ds.get("_name_", "genomic_benchmark")
     if name == "genomic_benchmark":

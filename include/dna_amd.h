@@ -24,8 +24,9 @@ extern "C" {
 
 #define DNA_AMD_ABI_VERSION 1
 /* Counts additions that leave every version-1 entry point as it was (a caller built against an
- * earlier revision keeps working): 1 = dna_lm_head_*, 2 = dna_lm_head_rc_*, 3 = dna_attn_varlen_*. */
-#define DNA_AMD_ABI_REVISION 3
+ * earlier revision keeps working): 1 = dna_lm_head_*, 2 = dna_lm_head_rc_*, 3 = dna_attn_varlen_*,
+ * 4 = dna_dconv_* / dna_onehot_conv_*. */
+#define DNA_AMD_ABI_REVISION 4
 
 enum dna_status {
   DNA_OK = 0,
@@ -37,7 +38,7 @@ enum dna_status {
 };
 
 enum dna_dtype { DNA_F32 = 0, DNA_BF16 = 1, DNA_F16 = 2 };
-enum dna_act { DNA_ACT_NONE = 0, DNA_ACT_GELU = 1 };
+enum dna_act { DNA_ACT_NONE = 0, DNA_ACT_GELU = 1, DNA_ACT_SIGMOID = 2 /* dna_dconv_* only */ };
 
 int dna_abi_version(void);
 int dna_abi_revision(void);
@@ -744,6 +745,68 @@ int dna_adamw_step(float* param, const float* grad, float* exp_avg, float* exp_a
                    void* param_bf16, size_t n, float lr, float beta1, float beta2, float eps,
                    float weight_decay, int step, const float* grad_sumsq, float max_grad_norm,
                    float grad_scale, void* stream);
+
+/* ------------------------------------------------------------------ gated dilated convolution
+ * The dense dilated Conv1d(C, C, K) pairs of the reference's CNNModel in mode "dilation"
+ * (src/models/sequence/denoise.py:468-486), channels-last, csrc/dilated_conv.hip. For x [B, L, C]
+ * (DNA_F32 or DNA_BF16), "same" padding, stride 1, c = (K - 1) / 2:
+ *   z[b, l, co] = bias[co] + sum_{t < K} sum_{ci} x[b, l + (t - c) dilation, ci] * W[co, ci, t]
+ * where a tap whose row falls outside [0, L) of its own sequence contributes 0 (so a dilation
+ * with c * dilation >= L leaves only the centre tap). The weight comes tap-major,
+ * w_taps [K, C, C] = W[co, ci, t] at (t * C + co) * C + ci, in the activation dtype. bf16 runs on
+ * v_mfma_f32_16x16x32_bf16 with fp32 accumulation, fp32 on plain FMAs. The epilogue rounds z to
+ * the activation dtype, then:
+ *   DNA_DCONV_PLAIN     out = act(z); z_out (optional) = z
+ *   DNA_DCONV_GATE      out = g = act(z); z_out (optional; the GELU gate's backward needs it) = z;
+ *                       res_out = g + res                                  (rc_feat = g + rc_feat)
+ *   DNA_DCONV_MAIN_MUL  z_out = z; res_out = gelu(z) * g + res             (forget)
+ *   DNA_DCONV_MAIN_ADD  z_out = z; res_out = gelu(z) + g + res
+ * g, out, z_out [B, L, C] in the activation dtype; res, res_out [B, L, C] fp32 (the residual
+ * streams stay fp32); bias [C] fp32 or NULL. act: DNA_ACT_NONE | DNA_ACT_GELU (erf form) |
+ * DNA_ACT_SIGMOID (MAIN_*: always GELU). The data gradient of z is the same call on dz with
+ * w_taps[t][ci][co] = W[co, ci, K - 1 - t], bias NULL, DNA_DCONV_PLAIN, DNA_ACT_NONE.
+ * C a multiple of 64 in [64, 512], K odd <= 9, dilation >= 1, B <= 65535, pointers 16-B aligned;
+ * anything else is DNA_ERR_INVALID and nothing is launched. */
+enum dna_dconv_epilogue {
+  DNA_DCONV_PLAIN = 0,
+  DNA_DCONV_GATE = 1,
+  DNA_DCONV_MAIN_MUL = 2,
+  DNA_DCONV_MAIN_ADD = 3
+};
+int dna_dconv_fwd(const void* x, int dtype, const void* w_taps, const float* bias, int B, int L,
+                  int C, int K, int dilation, int epilogue, int act, const void* g,
+                  const float* res, void* out, void* z_out, float* res_out, void* stream);
+/* Backward of the two epilogues of one layer, elementwise over n = B * L * C (n % 4 == 0):
+ *   forget:  dz_h = dfeat * g * gelu'(z_h);  dz_g = (dfeat * gelu(z_h) + drc) * g * (1 - g)
+ *   else:    dz_h = dfeat * gelu'(z_h);      dz_g = (dfeat + drc) * gelu'(z_g)
+ * dfeat, drc (NULL: zero) fp32: the gradients of the two new residual streams, which are also
+ * the gradients of the old ones; z_h, g, z_g (forget: unused, may be NULL), dz_h, dz_g in dtype. */
+int dna_dconv_bwd_elem(const float* dfeat, const float* drc, const void* z_h, const void* g,
+                       const void* z_g, int dtype, size_t n, int forget, void* dz_h, void* dz_g,
+                       void* stream);
+/* dW[co, ci, t] (+)= sum_{b, l} dz[b, l, co] * x[b, l + (t - c) dilation, ci] (fp32, the
+ * parameter's own [C, C, K] layout) and dbias[co] (+)= sum dz (NULL: skipped). The B * L rows are
+ * cut into dna_dconv_wgrad_splits() ranges whose fp32 partials (workspace, at least
+ * dna_dconv_wgrad_workspace() bytes) are summed in split order: no atomics, two runs give the
+ * same bits. accumulate != 0 adds to dw / dbias (the flat gradient buffer). */
+int dna_dconv_wgrad_splits(int B, int L, int C, int K);
+size_t dna_dconv_wgrad_workspace(int B, int L, int C, int K);
+int dna_dconv_wgrad(const void* dz, const void* x, int dtype, int B, int L, int C, int K,
+                    int dilation, float* dw, float* dbias, int accumulate, void* workspace,
+                    size_t workspace_bytes, void* stream);
+/* The input layer: Conv1d(V, C, KW, padding (KW - 1) / 2) on a one-hot input is a table lookup,
+ *   out[b, l, co] = act(bias[co] + sum_{t < KW} W[co, id[b, l + t - (KW - 1) / 2], t])
+ * ids [B, L] int64 (an id outside [0, V) or a position outside the row adds nothing), W [C, V, KW]
+ * and bias [C] fp32, out [B, L, C] fp32. complement != 0 reads 3 - id for id < 4 (A<->T, C<->G; N
+ * and anything above stay). V <= 8, KW odd <= 9, C % 64 == 0. The backward recomputes z and
+ * writes dw [C, V, KW] and dbias [C] from per-block partials summed in a fixed order. */
+int dna_onehot_conv_fwd(const int64_t* ids, const float* w, const float* bias, int B, int L, int C,
+                        int V, int KW, int complement, int act, float* out, void* stream);
+size_t dna_onehot_conv_bwd_workspace(int B, int L, int C, int V, int KW);
+int dna_onehot_conv_bwd(const int64_t* ids, const float* w, const float* bias, const float* dout,
+                        int B, int L, int C, int V, int KW, int complement, int act, float* dw,
+                        float* dbias, int accumulate, void* workspace, size_t workspace_bytes,
+                        void* stream);
 
 /* ------------------------------------------------------------------ data path (host, C++)
  * BPE tokenizer: bit-exact with the reference's HF `tokenizers` BPE for
