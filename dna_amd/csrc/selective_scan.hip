@@ -1316,10 +1316,23 @@ inline void allow_lds(K k, size_t bytes) {
   if (bytes > 65536) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
 }
 
+// The chunk-parallel kernels take a group of CW channels per block (and need the states buffer).
+inline bool plan_chunked(int dim) { return dim % CW == 0; }
+
+// carry_blk_kernel's dynamic LDS: the channel's [nch][N] summaries, [nch] delta sums and the two
+// [SEG][N] segment tables (SEG * N = 256).
+inline size_t carry_blk_bytes(int nch, int n) {
+  return ((size_t)nch * (n + 1) + 2 * 256) * sizeof(float);
+}
+// Which carry kernel runs: the block kernel while its LDS image fits 64 KB, else the wave-per-
+// (channel, state) kernel, which keeps nothing in LDS. launch_carry and dna_selective_scan_plan
+// both decide here.
+inline bool plan_carry_par(int nch, int n) { return carry_blk_bytes(nch, n) > 65536; }
+
 template <int NS>
 inline void launch_carry(const Args& a, const Chunked& q, int reverse, hipStream_t s) {
-  const size_t bytes = ((size_t)q.nch * (NS + 1) + 2 * 256) * sizeof(float);
-  if (bytes <= 65536) {
+  const size_t bytes = carry_blk_bytes(q.nch, NS);
+  if (!plan_carry_par(q.nch, NS)) {
     hipLaunchKernelGGL((carry_blk_kernel<NS>), dim3(a.batch * a.dim), dim3(256), bytes, s, a, q, reverse);
   } else {
     hipLaunchKernelGGL((carry_par_kernel<NS>), dim3(a.batch * a.dim * NS), dim3(64), 0, s, a, q, reverse);
@@ -1348,6 +1361,20 @@ extern "C" size_t dna_selective_scan_states(int batch, int dim, int len, int d_s
   return (size_t)batch * dim * ((len + CHUNK - 1) / CHUNK) * (2 * d_state + 1);
 }
 
+extern "C" int dna_selective_scan_plan(int batch, int dim, int len, int d_state, int* chunked,
+                                       int* k, int* nch, int* carry_par) {
+  DNA_CHECK_ARG(batch > 0 && dim > 0 && len > 0, "dna_selective_scan_plan: bad shape");
+  DNA_CHECK_ARG(d_state == 4 || d_state == 8 || d_state == 16,
+                "dna_selective_scan_plan: d_state %d unsupported (4, 8, 16)", d_state);
+  const bool ck = plan_chunked(dim);
+  const Chunked q = plan_chunks(batch, dim, len);
+  if (chunked) *chunked = ck;
+  if (k) *k = ck ? q.k : 0;
+  if (nch) *nch = ck ? q.nch : 0;
+  if (carry_par) *carry_par = ck && plan_carry_par(q.nch, d_state);
+  return DNA_OK;
+}
+
 extern "C" int dna_selective_scan_fwd(const void* u, const void* delta, const float* A, const void* B,
                                       const void* C, const float* D, const void* z,
                                       const float* delta_bias, int delta_softplus, int dtype,
@@ -1360,7 +1387,7 @@ extern "C" int dna_selective_scan_fwd(const void* u, const void* delta, const fl
   a.softplus = delta_softplus; a.batch = batch; a.dim = dim; a.len = len;
   a.out = out; a.states = states; a.last_state = last_state;
   hipStream_t s = as_stream(stream);
-  const bool chunked = states && dim % CW == 0;
+  const bool chunked = states && plan_chunked(dim);
   auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
   const bool vec = len % ITEMS == 0 && al16(u) && al16(delta) && al16(out) && (!z || al16(z));
   const Chunked q = plan_chunks(batch, dim, len);
@@ -1403,7 +1430,7 @@ extern "C" int dna_selective_scan_bwd(const void* u, const void* delta, const fl
   a.dout = dout; a.du = du; a.ddelta = ddelta; a.dz = dz; a.dA = dA; a.dB = dB; a.dC = dC;
   a.dD = dD; a.ddelta_bias = ddelta_bias;
   hipStream_t s = as_stream(stream);
-  const bool chunked = dim % CW == 0;
+  const bool chunked = plan_chunked(dim);
   auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
   // rows of whole 16-B vectors: the chunk backward's branch-free buffer I/O
   const bool vec = len % ITEMS == 0 && al16(u) && al16(delta) && al16(dout) && al16(du) &&

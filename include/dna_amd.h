@@ -25,8 +25,8 @@ extern "C" {
 #define DNA_AMD_ABI_VERSION 1
 /* Counts additions that leave every version-1 entry point as it was (a caller built against an
  * earlier revision keeps working): 1 = dna_lm_head_*, 2 = dna_lm_head_rc_*, 3 = dna_attn_varlen_*,
- * 4 = dna_dconv_* / dna_onehot_conv_*. */
-#define DNA_AMD_ABI_REVISION 4
+ * 4 = dna_dconv_* / dna_onehot_conv_*, 5 = dna_selective_scan_plan. */
+#define DNA_AMD_ABI_REVISION 5
 
 enum dna_status {
   DNA_OK = 0,
@@ -548,6 +548,13 @@ int dna_selective_scan_bwd(const void* u, const void* delta, const float* A, con
                            float* states, const void* dout, void* du, void* ddelta,
                            float* dA, float* dB, float* dC, float* dD, void* dz,
                            float* ddelta_bias, void* stream);
+/* Host-only query of the dispatch the two calls above take for a shape (no GPU work; any output
+ * pointer may be NULL): *chunked = 1 when the chunk-parallel kernels run (given a states buffer),
+ * 0 for the per-channel kernels; then *k = channels per wave (1, 2, 4, 8), *nch = chunks per row,
+ * *carry_par = 1 when the chunk carries run in carry_par_kernel, 0 in carry_blk_kernel. All three
+ * are 0 when *chunked is 0. */
+int dna_selective_scan_plan(int batch, int dim, int len, int d_state, int* chunked, int* k,
+                            int* nch, int* carry_par);
 
 /* ------------------------------------------------------------------ masked-LM cross entropy
  * Per-row CE over the masked rows only (the model computes logits only for labels>0 rows,
