@@ -16,7 +16,7 @@ LIB_PATH = os.environ.get("DNA_AMD_LIB", os.path.join(_HERE, "lib", "libdna_amd.
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "dna_amd.h")
 
 F32, BF16, F16 = 0, 1, 2
-ACT_NONE, ACT_GELU, ACT_SIGMOID = 0, 1, 2
+ACT_NONE, ACT_GELU, ACT_SIGMOID, ACT_RELU = 0, 1, 2, 3
 DCONV_PLAIN, DCONV_GATE, DCONV_MAIN_MUL, DCONV_MAIN_ADD = 0, 1, 2, 3
 CLS_REGRESSION, CLS_SINGLE_LABEL, CLS_MULTI_LABEL = 0, 1, 2
 
@@ -147,6 +147,11 @@ _SIGS = {
     "dna_lm_head_bwd_workspace": (_sz, [_i, _i, _i]),
     "dna_lm_head_bwd": (_i, [_vp, _vp, _i64, _i, _vp, _i, _vp, _vp, _vp, _f, _i, _i, _i, _vp, _i64,
                              _vp, _i, _vp, _sz, _vp]),
+    "dna_lm_head_bias_fwd": (_i, [_vp, _i64, _i, _vp, _i, _vp, _vp, _i, _i, _i, _f, _vp, _vp, _vp,
+                                  _vp, _vp, _sz, _vp]),
+    "dna_lm_head_bias_bwd_workspace": (_sz, [_i, _i, _i]),
+    "dna_lm_head_bias_bwd": (_i, [_vp, _vp, _i64, _i, _vp, _i, _vp, _vp, _vp, _f, _i, _i, _i, _vp,
+                                  _i64, _vp, _vp, _i, _vp, _sz, _vp]),
     "dna_lm_head_rc_fwd_workspace": (_sz, [_i, _i, _i]),
     "dna_lm_head_rc_fwd": (_i, [_vp, _i64, _i, _vp, _i, _vp, _vp, _i, _i, _i, _f, _vp, _vp, _vp,
                                 _vp, _vp, _sz, _vp]),

@@ -416,7 +416,7 @@ __global__ __launch_bounds__(256) void onehot_fwd_kernel(const int64_t* __restri
       const int id = oh_id(ids, row + t - c, V, complement);
       if (id >= 0) z += tab[(id * KW + t) * 64 + col];
     }
-    out[(size_t)row * C + co0 + col] = apply_act(z, act);
+    out[(size_t)row * C + co0 + col] = act == DNA_ACT_RELU ? fmaxf(z, 0.f) : apply_act(z, act);
   }
 }
 
@@ -454,6 +454,7 @@ __global__ __launch_bounds__(64) void onehot_bwd_kernel(const int64_t* __restric
     float d = dout[(size_t)row * C + co0 + col];
     if (act == DNA_ACT_GELU) d *= gelu_erf_grad(z);
     else if (act == DNA_ACT_SIGMOID) { const float s = sigm(z); d *= s * (1.f - s); }
+    else if (act == DNA_ACT_RELU) d = z > 0.f ? d : 0.f;
     bsum += d;
 #pragma unroll
     for (int t = 0; t < OH_MAXK; ++t)
@@ -624,7 +625,8 @@ extern "C" int dna_onehot_conv_fwd(const int64_t* ids, const float* w, const flo
   DNA_CHECK_ARG(onehot_ok(B, L, C, V, KW),
                 "dna_onehot_conv_fwd: B=%d L=%d C=%d V=%d KW=%d unsupported (C %% 64 == 0, V <= 8, "
                 "KW odd <= 9)", B, L, C, V, KW);
-  DNA_CHECK_ARG(act == DNA_ACT_NONE || act == DNA_ACT_GELU || act == DNA_ACT_SIGMOID,
+  DNA_CHECK_ARG(act == DNA_ACT_NONE || act == DNA_ACT_GELU || act == DNA_ACT_SIGMOID ||
+                    act == DNA_ACT_RELU,
                 "dna_onehot_conv_fwd: act %d", act);
   const long long R = (long long)B * L;
   DNA_CHECK_ARG((R + 15) / 16 < (1ll << 31), "dna_onehot_conv_fwd: too many rows");
@@ -652,7 +654,8 @@ extern "C" int dna_onehot_conv_bwd(const int64_t* ids, const float* w, const flo
   DNA_CHECK_ARG(ids && w && dout && dw && workspace, "dna_onehot_conv_bwd: null pointer");
   DNA_CHECK_ARG(onehot_ok(B, L, C, V, KW),
                 "dna_onehot_conv_bwd: B=%d L=%d C=%d V=%d KW=%d unsupported", B, L, C, V, KW);
-  DNA_CHECK_ARG(act == DNA_ACT_NONE || act == DNA_ACT_GELU || act == DNA_ACT_SIGMOID,
+  DNA_CHECK_ARG(act == DNA_ACT_NONE || act == DNA_ACT_GELU || act == DNA_ACT_SIGMOID ||
+                    act == DNA_ACT_RELU,
                 "dna_onehot_conv_bwd: act %d", act);
   DNA_CHECK_ARG(workspace_bytes >= dna_onehot_conv_bwd_workspace(B, L, C, V, KW),
                 "dna_onehot_conv_bwd: workspace too small");

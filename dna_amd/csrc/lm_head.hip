@@ -35,6 +35,12 @@
 // gradient of Wt back to W: dW[u, d] (+)= dWt[u, d] + sum over v with cm[v] == u, v ascending,
 // of dWt[v, 2D-1-d] -- the backward of the gather W[cm], whatever cm is (not an involution, not
 // injective), one thread per element, a fixed order, no atomics.
+//
+// Biased head (the CNN's untied out_linear; dna_lm_head_bias_*): logit_v += bias[v], one fp32 add
+// after the row's sum, and dbias[v] = g / count * sum_r coef_r,v. dw_part_kernel takes the bias as
+// column D of an h whose extra column is 1: the same chunks, the same lists, the same order; its
+// partials go to their own [chunks][V] block and dw_finish_kernel sums them. A null bias runs the
+// kernels above exactly as before.
 #include <math.h>
 
 #include "common.h"
@@ -102,7 +108,8 @@ __device__ __forceinline__ uint64_t wave_rows(const int64_t* labels, int64_t bas
 
 // ------------------------------------------------------------------------------------- forward
 struct RowArgs {
-  const void* h; int64_t hs; const void* W; const int64_t* labels;
+  const void* h; int64_t hs; const void* W; const float* bias;  // bias [V] fp32; NULL: none
+  const int64_t* labels;
   int T, D, V;
   float* coef;                        // [T][V], kept rows only; NULL: not wanted
   double* part_loss; int64_t* part_cnt;  // [workgroups]
@@ -184,7 +191,8 @@ __global__ __launch_bounds__(TPB) void rows_kernel(RowArgs g) {
     m &= m - 1;
     const int y = __shfl(label, i);
     const int64_t r = base + i;
-    const float logit = row_logits<HBF, WBF, VEC, REG>(g.h, r * g.hs, g.W, g.D, g.V, lane);
+    float logit = row_logits<HBF, WBF, VEC, REG>(g.h, r * g.hs, g.W, g.D, g.V, lane);
+    if (g.bias && lane < g.V) logit += g.bias[lane];
     const float mx = wave_max(logit);
     const float e = lane < g.V ? expf(logit - mx) : 0.f;
     const float s = wave_sum(e);
@@ -295,12 +303,14 @@ __global__ __launch_bounds__(TPB) void dh_kernel(DhArgs g) {
 struct DwArgs {
   const float* coef; const void* h; int64_t hs; const int64_t* labels;
   int T, D, V, chunk_len;
-  float* part;  // [chunks][V][D]
+  float* part;    // [chunks][V][D]
+  float* part_b;  // [chunks][V]: the bias column (column D, h = 1); NULL: not wanted
 };
 
 // Workgroup (x, y): columns 256 x .. of chunk y's rows. Per 256 rows the kept ones are listed in
 // index order (ballot + prefix counts), then a thread adds coef_r,v h[r, d] over the list into
-// its V sums; coef_r,: is read through scalar loads (the row is the same in every lane).
+// its V sums; coef_r,: is read through scalar loads (the row is the same in every lane). With
+// part_b the grid covers D + 1 columns and column D sums coef_r,v alone (the bias gradient).
 template <bool HBF, int VMAX>
 __global__ __launch_bounds__(TPB) void dw_part_kernel(DwArgs g) {
   __shared__ int list[TPB];
@@ -310,6 +320,7 @@ __global__ __launch_bounds__(TPB) void dw_part_kernel(DwArgs g) {
   const int chunk = blockIdx.y;
   const int64_t r0 = (int64_t)chunk * g.chunk_len;
   const int64_t r1 = min(r0 + g.chunk_len, (int64_t)g.T);
+  const int ncol = g.part_b ? g.D + 1 : g.D;
   float acc[VMAX];
 #pragma unroll
   for (int v = 0; v < VMAX; ++v) acc[v] = 0.f;
@@ -330,7 +341,7 @@ __global__ __launch_bounds__(TPB) void dw_part_kernel(DwArgs g) {
     }
     if (keep) list[off + __popcll(b & ((1ull << lane) - 1ull))] = tid;
     __syncthreads();
-    if (d < g.D) {
+    if (d < ncol) {
       // eight listed rows at a time: their loads are issued before the first is used; the
       // sums still take the rows in list order
       for (int i0 = 0; i0 < n; i0 += 8) {
@@ -339,8 +350,9 @@ __global__ __launch_bounds__(TPB) void dw_part_kernel(DwArgs g) {
 #pragma unroll
         for (int u = 0; u < 8; ++u) {
           rr[u] = sb + __builtin_amdgcn_readfirstlane(list[min(i0 + u, n - 1)]);
-          hv[u] = HBF ? (float)reinterpret_cast<const bf16*>(g.h)[rr[u] * g.hs + d]
-                      : reinterpret_cast<const float*>(g.h)[rr[u] * g.hs + d];
+          if (d == g.D) hv[u] = 1.f;
+          else hv[u] = HBF ? (float)reinterpret_cast<const bf16*>(g.h)[rr[u] * g.hs + d]
+                           : reinterpret_cast<const float*>(g.h)[rr[u] * g.hs + d];
         }
 #pragma unroll
         for (int u = 0; u < 8; ++u) {
@@ -359,6 +371,10 @@ __global__ __launch_bounds__(TPB) void dw_part_kernel(DwArgs g) {
 #pragma unroll
     for (int v = 0; v < VMAX; ++v)
       if (v < g.V) g.part[((int64_t)chunk * g.V + v) * g.D + d] = acc[v];
+  } else if (d == g.D && g.part_b) {
+#pragma unroll
+    for (int v = 0; v < VMAX; ++v)
+      if (v < g.V) g.part_b[(int64_t)chunk * g.V + v] = acc[v];
   }
 }
 
@@ -472,18 +488,18 @@ extern "C" size_t dna_lm_head_fwd_workspace(int T) {
   return (size_t)lmh::row_blocks(T) * (sizeof(double) + sizeof(int64_t));
 }
 
-extern "C" int dna_lm_head_fwd(const void* h, int64_t h_stride, int h_dtype, const void* W,
-                               int w_dtype, const int64_t* labels, int T, int D, int V,
-                               float denom, float* loss_sum, int64_t* count, float* loss,
-                               float* coef, void* workspace, size_t workspace_bytes,
-                               void* stream) {
-  int st = lmh::shape_check("dna_lm_head_fwd", T, D, V, h_dtype, w_dtype);
+// dna_lm_head_fwd (bias NULL) and dna_lm_head_bias_fwd
+static int head_fwd(const char* name, const void* h, int64_t h_stride, int h_dtype, const void* W,
+                    int w_dtype, const float* bias, const int64_t* labels, int T, int D, int V,
+                    float denom, float* loss_sum, int64_t* count, float* loss, float* coef,
+                    void* workspace, size_t workspace_bytes, void* stream) {
+  int st = lmh::shape_check(name, T, D, V, h_dtype, w_dtype);
   if (st != DNA_OK) return st;
-  DNA_CHECK_ARG(h && W && labels && loss_sum && count, "dna_lm_head_fwd: null pointer");
-  DNA_CHECK_ARG(h_stride >= D, "dna_lm_head_fwd: row stride must be >= D");
+  DNA_CHECK_ARG(h && W && labels && loss_sum && count, "%s: null pointer", name);
+  DNA_CHECK_ARG(h_stride >= D, "%s: row stride must be >= D", name);
   const size_t need = dna_lm_head_fwd_workspace(T);
   DNA_CHECK_ARG(workspace && workspace_bytes >= need && aligned(workspace, 8),
-                "dna_lm_head_fwd: workspace too small or not 8-byte aligned (%zu < %zu)",
+                "%s: workspace too small or not 8-byte aligned (%zu < %zu)", name,
                 workspace_bytes, need);
   hipStream_t s = as_stream(stream);
   const int nb = lmh::row_blocks(T);
@@ -491,7 +507,7 @@ extern "C" int dna_lm_head_fwd(const void* h, int64_t h_stride, int h_dtype, con
   const bool reg = D <= lmh::NCH * 64 * vec;
   double* part_loss = (double*)workspace;
   int64_t* part_cnt = (int64_t*)(part_loss + nb);
-  lmh::RowArgs ra{h, h_stride, W, labels, T, D, V, coef, part_loss, part_cnt};
+  lmh::RowArgs ra{h, h_stride, W, bias, labels, T, D, V, coef, part_loss, part_cnt};
   const dim3 grid((unsigned)nb);
   if (h_dtype == DNA_BF16) {
     if (w_dtype == DNA_BF16) lmh::launch_rows<true, true>(vec, reg, grid, s, ra);
@@ -500,11 +516,29 @@ extern "C" int dna_lm_head_fwd(const void* h, int64_t h_stride, int h_dtype, con
     if (w_dtype == DNA_BF16) lmh::launch_rows<false, true>(vec, reg, grid, s, ra);
     else lmh::launch_rows<false, false>(vec, reg, grid, s, ra);
   }
-  DNA_LAUNCH_CHECK("dna_lm_head_fwd");
+  DNA_LAUNCH_CHECK(name);
   hipLaunchKernelGGL(lmh::finish_kernel, dim3(1), dim3(1024), 0, s, (const double*)part_loss,
                      (const int64_t*)part_cnt, nb, denom, loss_sum, count, loss);
-  DNA_LAUNCH_CHECK("dna_lm_head_fwd");
+  DNA_LAUNCH_CHECK(name);
   return DNA_OK;
+}
+
+extern "C" int dna_lm_head_fwd(const void* h, int64_t h_stride, int h_dtype, const void* W,
+                               int w_dtype, const int64_t* labels, int T, int D, int V,
+                               float denom, float* loss_sum, int64_t* count, float* loss,
+                               float* coef, void* workspace, size_t workspace_bytes,
+                               void* stream) {
+  return head_fwd("dna_lm_head_fwd", h, h_stride, h_dtype, W, w_dtype, nullptr, labels, T, D, V,
+                  denom, loss_sum, count, loss, coef, workspace, workspace_bytes, stream);
+}
+
+extern "C" int dna_lm_head_bias_fwd(const void* h, int64_t h_stride, int h_dtype, const void* W,
+                                    int w_dtype, const float* bias, const int64_t* labels, int T,
+                                    int D, int V, float denom, float* loss_sum, int64_t* count,
+                                    float* loss, float* coef, void* workspace,
+                                    size_t workspace_bytes, void* stream) {
+  return head_fwd("dna_lm_head_bias_fwd", h, h_stride, h_dtype, W, w_dtype, bias, labels, T, D, V,
+                  denom, loss_sum, count, loss, coef, workspace, workspace_bytes, stream);
 }
 
 extern "C" size_t dna_lm_head_bwd_workspace(int T, int D, int V) {
@@ -512,18 +546,24 @@ extern "C" size_t dna_lm_head_bwd_workspace(int T, int D, int V) {
   return (size_t)lmh::dw_nchunks(T) * V * D * sizeof(float);
 }
 
-extern "C" int dna_lm_head_bwd(const float* coef, const void* h, int64_t h_stride, int h_dtype,
-                               const void* W, int w_dtype, const int64_t* labels,
-                               const int64_t* count, const float* upstream, float denom, int T,
-                               int D, int V, void* dh, int64_t dh_stride, float* dW,
-                               int accumulate, void* workspace, size_t workspace_bytes,
-                               void* stream) {
-  int st = lmh::shape_check("dna_lm_head_bwd", T, D, V, h_dtype, w_dtype);
+extern "C" size_t dna_lm_head_bias_bwd_workspace(int T, int D, int V) {
+  if (T < 1 || D < 1 || V < 1) return 0;
+  return dna_lm_head_bwd_workspace(T, D, V) + (size_t)lmh::dw_nchunks(T) * V * sizeof(float);
+}
+
+// dna_lm_head_bwd (db NULL) and dna_lm_head_bias_bwd; workspace: dW's partials, then db's
+static int head_bwd(const char* name, const float* coef, const void* h, int64_t h_stride,
+                    int h_dtype, const void* W, int w_dtype, const int64_t* labels,
+                    const int64_t* count, const float* upstream, float denom, int T, int D, int V,
+                    void* dh, int64_t dh_stride, float* dW, float* db, int accumulate,
+                    void* workspace, size_t workspace_bytes, void* stream) {
+  int st = lmh::shape_check(name, T, D, V, h_dtype, w_dtype);
   if (st != DNA_OK) return st;
-  DNA_CHECK_ARG(coef && W && labels && count, "dna_lm_head_bwd: null pointer");
-  DNA_CHECK_ARG(!dh || dh_stride >= D, "dna_lm_head_bwd: dh row stride must be >= D");
-  DNA_CHECK_ARG(!dW || (h && h_stride >= D), "dna_lm_head_bwd: dW needs h with a row stride >= D");
-  DNA_CHECK_ARG((int64_t)V * D <= 0x7fffffff, "dna_lm_head_bwd: V * D too large");
+  DNA_CHECK_ARG(coef && W && labels && count, "%s: null pointer", name);
+  DNA_CHECK_ARG(!dh || dh_stride >= D, "%s: dh row stride must be >= D", name);
+  DNA_CHECK_ARG(!dW || (h && h_stride >= D), "%s: dW needs h with a row stride >= D", name);
+  DNA_CHECK_ARG(!db || dW, "%s: dbias is computed with dW only", name);
+  DNA_CHECK_ARG((int64_t)V * D <= 0x7fffffff, "%s: V * D too large", name);
   hipStream_t s = as_stream(stream);
   if (dh) {
     lmh::DhArgs da{coef, W, labels, count, upstream, denom, T, D, V, dh, dh_stride};
@@ -536,24 +576,55 @@ extern "C" int dna_lm_head_bwd(const float* coef, const void* h, int64_t h_strid
       if (w_dtype == DNA_BF16) lmh::launch_dh<false, true>(vec, grid, s, da);
       else lmh::launch_dh<false, false>(vec, grid, s, da);
     }
-    DNA_LAUNCH_CHECK("dna_lm_head_bwd");
+    DNA_LAUNCH_CHECK(name);
   }
   if (!dW) return DNA_OK;  // a frozen embedding
-  const size_t need = dna_lm_head_bwd_workspace(T, D, V);
-  DNA_CHECK_ARG(workspace && workspace_bytes >= need,
-                "dna_lm_head_bwd: workspace too small (%zu < %zu)", workspace_bytes, need);
+  const size_t need = db ? dna_lm_head_bias_bwd_workspace(T, D, V) : dna_lm_head_bwd_workspace(T, D, V);
+  DNA_CHECK_ARG(workspace && workspace_bytes >= need, "%s: workspace too small (%zu < %zu)", name,
+                workspace_bytes, need);
   const int nchunks = lmh::dw_nchunks(T);
-  lmh::DwArgs wa{coef, h, h_stride, labels, T, D, V, lmh::dw_chunk_len(T), (float*)workspace};
-  const dim3 grid((unsigned)((D + lmh::TPB - 1) / lmh::TPB), (unsigned)nchunks);
+  float* part = (float*)workspace;
+  float* part_b = db ? part + (size_t)nchunks * V * D : nullptr;
+  lmh::DwArgs wa{coef, h, h_stride, labels, T, D, V, lmh::dw_chunk_len(T), part, part_b};
+  const int ncol = db ? D + 1 : D;
+  const dim3 grid((unsigned)((ncol + lmh::TPB - 1) / lmh::TPB), (unsigned)nchunks);
   if (h_dtype == DNA_BF16) lmh::launch_dw<true>(V, grid, s, wa);
   else lmh::launch_dw<false>(V, grid, s, wa);
-  DNA_LAUNCH_CHECK("dna_lm_head_bwd");
+  DNA_LAUNCH_CHECK(name);
   const int n = V * D;
   hipLaunchKernelGGL(lmh::dw_finish_kernel, dim3((unsigned)((n + lmh::TPB - 1) / lmh::TPB)),
-                     dim3(lmh::TPB), 0, s, (const float*)workspace, nchunks, n, count, upstream,
-                     denom, dW, accumulate ? 1 : 0);
-  DNA_LAUNCH_CHECK("dna_lm_head_bwd");
+                     dim3(lmh::TPB), 0, s, (const float*)part, nchunks, n, count, upstream, denom,
+                     dW, accumulate ? 1 : 0);
+  DNA_LAUNCH_CHECK(name);
+  if (db) {
+    hipLaunchKernelGGL(lmh::dw_finish_kernel, dim3(1), dim3(lmh::TPB), 0, s, (const float*)part_b,
+                       nchunks, V, count, upstream, denom, db, accumulate ? 1 : 0);
+    DNA_LAUNCH_CHECK(name);
+  }
   return DNA_OK;
+}
+
+extern "C" int dna_lm_head_bwd(const float* coef, const void* h, int64_t h_stride, int h_dtype,
+                               const void* W, int w_dtype, const int64_t* labels,
+                               const int64_t* count, const float* upstream, float denom, int T,
+                               int D, int V, void* dh, int64_t dh_stride, float* dW,
+                               int accumulate, void* workspace, size_t workspace_bytes,
+                               void* stream) {
+  return head_bwd("dna_lm_head_bwd", coef, h, h_stride, h_dtype, W, w_dtype, labels, count,
+                  upstream, denom, T, D, V, dh, dh_stride, dW, nullptr, accumulate, workspace,
+                  workspace_bytes, stream);
+}
+
+extern "C" int dna_lm_head_bias_bwd(const float* coef, const void* h, int64_t h_stride,
+                                    int h_dtype, const void* W, int w_dtype,
+                                    const int64_t* labels, const int64_t* count,
+                                    const float* upstream, float denom, int T, int D, int V,
+                                    void* dh, int64_t dh_stride, float* dW, float* dbias,
+                                    int accumulate, void* workspace, size_t workspace_bytes,
+                                    void* stream) {
+  return head_bwd("dna_lm_head_bias_bwd", coef, h, h_stride, h_dtype, W, w_dtype, labels, count,
+                  upstream, denom, T, D, V, dh, dh_stride, dW, dbias, accumulate, workspace,
+                  workspace_bytes, stream);
 }
 
 // ------------------------------------------------------------------------ RC-equivariant head

@@ -877,12 +877,17 @@ class MaskedLMHead(torch.autograd.Function):
     cm [V] int64 on the device (Caduceus' RCPSLMHead.complement_map, its entries validated on the
     host where the module builds it): the RC-equivariant head. h is then [T, 2 D] and
     logits = h[:, :D] w^T + flip(h[:, D:]) w[cm]^T; dw folds the gathered rows' gradient back in a
-    fixed order (dna_lm_head_rc_*)."""
+    fixed order (dna_lm_head_rc_*).
+
+    bias [V] fp32 (with cm None only): an untied, biased head (the CNN's out_linear),
+    logits = h w^T + bias on dna_lm_head_bias_*; its gradient goes where dw goes."""
 
     @staticmethod
-    def forward(ctx, h, w, labels, denom, cm=None):
+    def forward(ctx, h, w, labels, denom, cm=None, bias=None):
         _gpu(h, w, labels)
         ctx.set_materialize_grads(False)
+        if bias is not None and cm is not None:
+            raise ValueError("dna_amd: the RC-equivariant lm head (complement_map) takes no bias")
         if h.dim() != 2 or h.numel() == 0:
             raise ValueError(f"dna_amd: lm head input must be a non-empty [T, D], got {tuple(h.shape)}")
         T, Dh = h.shape
@@ -902,6 +907,11 @@ class MaskedLMHead(torch.autograd.Function):
         if labels.dtype != torch.int64 or labels.numel() != T:
             raise TypeError(f"dna_amd: lm head labels must be int64 [{T}], got {labels.dtype} "
                             f"{tuple(labels.shape)}")
+        if bias is not None:
+            _gpu(bias)
+            if bias.dtype != torch.float32 or not bias.is_contiguous() or tuple(bias.shape) != (V,):
+                raise TypeError(f"dna_amd: lm head bias must be contiguous fp32 [{V}], got "
+                                f"{bias.dtype} {tuple(bias.shape)}")
         if cm is not None:
             _gpu(cm)
             if cm.dtype != torch.int64 or cm.numel() != V:
@@ -912,12 +922,21 @@ class MaskedLMHead(torch.autograd.Function):
         lp = getattr(w, "_dna_lp", None)
         wk = lp if (h.dtype == torch.bfloat16 and lp is not None) else w
         dev = h.device
-        need_bwd = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
+        need_bwd = (ctx.needs_input_grad[0] or ctx.needs_input_grad[1] or
+                    (bias is not None and ctx.needs_input_grad[5]))
         out = torch.empty(2, device=dev, dtype=torch.float32)  # loss_sum, loss
         count = torch.empty((), device=dev, dtype=torch.int64)
         coef = torch.empty(T, V, device=dev, dtype=torch.float32) if need_bwd else None
         dn = 0.0 if denom is None else float(denom)
-        if cm is None:
+        if bias is not None:
+            nws = N.lib().dna_lm_head_fwd_workspace(T)
+            ws = torch.empty(max(nws // 8, 2), device=dev, dtype=torch.float64)
+            with _timed("lm_head_bias_fwd", float(T) * D * h.element_size(), kind="byte"):
+                N.call("dna_lm_head_bias_fwd", h.data_ptr(), hs, _dt(h), wk.data_ptr(), _dt(wk),
+                       bias.data_ptr(), labels.data_ptr(), T, D, V, dn, out.data_ptr(),
+                       count.data_ptr(), out[1:].data_ptr(), _p(coef), ws.data_ptr(),
+                       ws.numel() * 8, N.stream_ptr())
+        elif cm is None:
             nws = N.lib().dna_lm_head_fwd_workspace(T)
             ws = torch.empty(max(nws // 8, 2), device=dev, dtype=torch.float64)
             with _timed("lm_head_fwd", float(T) * D * h.element_size(), kind="byte"):
@@ -934,6 +953,7 @@ class MaskedLMHead(torch.autograd.Function):
                        ws.numel() * 8, N.stream_ptr())
         ctx.save_for_backward(h, wk, labels, count, coef, cm)
         ctx.param = w
+        ctx.bias = bias
         ctx.cfg = (hs, dn)
         ctx.mark_non_differentiable(count)
         return out[1], count
@@ -942,21 +962,30 @@ class MaskedLMHead(torch.autograd.Function):
     def backward(ctx, dloss, dcount):
         h, wk, labels, count, coef, cm = ctx.saved_tensors
         if dloss is None or coef is None:
-            return None, None, None, None, None
+            return None, None, None, None, None, None
         hs, dn = ctx.cfg
         T, Dh = h.shape
         V, D = wk.shape
         dev = h.device
         up = dloss.detach().to(torch.float32).reshape(1).contiguous()
-        w = ctx.param
-        direct = _param_grads_direct((w,))
-        dw = None
+        w, b = ctx.param, ctx.bias
+        direct = _param_grads_direct((w, b))
+        dw = db = None
         if direct:
-            dw = w.grad
-        elif ctx.needs_input_grad[1]:
+            dw, db = w.grad, None if b is None else b.grad
+        elif ctx.needs_input_grad[1] or (b is not None and ctx.needs_input_grad[5]):
             dw = torch.empty(V, D, device=dev, dtype=torch.float32)
+            db = None if b is None else torch.empty(V, device=dev, dtype=torch.float32)
         dh = torch.empty(T, Dh, device=dev, dtype=h.dtype) if ctx.needs_input_grad[0] else None
-        if cm is None:
+        if b is not None:
+            nws = N.lib().dna_lm_head_bias_bwd_workspace(T, D, V) if dw is not None else 0
+            ws = torch.empty(max(nws // 4, 4), device=dev, dtype=torch.float32)
+            with _timed("lm_head_bias_bwd", float(T) * D * h.element_size(), kind="byte"):
+                N.call("dna_lm_head_bias_bwd", coef.data_ptr(), h.data_ptr(), hs, _dt(h),
+                       wk.data_ptr(), _dt(wk), labels.data_ptr(), count.data_ptr(), up.data_ptr(),
+                       dn, T, D, V, _p(dh), D, _p(dw), _p(db), int(direct), ws.data_ptr(),
+                       ws.numel() * 4, N.stream_ptr())
+        elif cm is None:
             nws = N.lib().dna_lm_head_bwd_workspace(T, D, V) if dw is not None else 0
             ws = torch.empty(max(nws // 4, 4), device=dev, dtype=torch.float32)
             with _timed("lm_head_bwd", float(T) * D * h.element_size(), kind="byte"):
@@ -973,18 +1002,21 @@ class MaskedLMHead(torch.autograd.Function):
                        up.data_ptr(), dn, T, D, V, _p(dh), Dh, _p(dw), int(direct), ws.data_ptr(),
                        ws.numel() * 4, N.stream_ptr())
         if direct:
-            _notify_direct(w)
-            return dh, None, None, None, None
-        return dh, dw, None, None, None
+            _notify_direct(w, b)
+            return dh, None, None, None, None, None
+        return dh, dw, None, None, None, db
 
 
-def masked_lm_head(h, weight, labels, denom=None, complement_map=None):
+def masked_lm_head(h, weight, labels, denom=None, complement_map=None, bias=None):
     """MaskedLMHead outside autocast (the kernels take h in its own dtype, so the result is the
     same with and without it). h [..., D], labels [...] -> (loss, count). complement_map [V]
-    (int64, on the device): the RC-equivariant head; h then has 2 * D columns."""
+    (int64, on the device): the RC-equivariant head; h then has 2 * D columns. bias [V] fp32: the
+    biased head (complement_map None only)."""
+    if bias is not None and complement_map is not None:
+        raise ValueError("dna_amd: the RC-equivariant lm head (complement_map) takes no bias")
     with torch.autocast("cuda", enabled=False):
         return MaskedLMHead.apply(h.reshape(-1, h.shape[-1]), weight, labels.reshape(-1), denom,
-                                  complement_map)
+                                  complement_map, bias)
 
 
 # ----------------------------------------------------------------------------------- cls head
@@ -1968,23 +2000,26 @@ class GatedDilatedConv(torch.autograd.Function):
 
 
 class OneHotConv(torch.autograd.Function):
-    """gelu(Conv1d(V, C, KW, padding (KW - 1) / 2)(one_hot(ids))) -> [B, L, C] fp32 as a table
+    """act(Conv1d(V, C, KW, padding (KW - 1) / 2)(one_hot(ids))) -> [B, L, C] fp32 as a table
     lookup (dna_onehot_conv_fwd); complement: on 3 - id for id < 4 (N stays). The backward
     recomputes z and sums the [C, V, KW] gradient from per-block partials in a fixed order."""
 
     @staticmethod
-    def forward(ctx, ids, w, b, complement):
+    def forward(ctx, ids, w, b, complement, act=N.ACT_GELU):
         _gpu(ids, w, b)
+        if act not in (N.ACT_GELU, N.ACT_RELU):
+            raise ValueError(f"dna_amd: onehot_conv act must be ACT_GELU or ACT_RELU, got {act}")
         ids = ids.to(torch.int64).contiguous()
         B, L = ids.shape
         C, V, KW = w.shape
         w32, b32 = w.detach().float().contiguous(), None if b is None else b.detach().float().contiguous()
         out = torch.empty(B, L, C, device=ids.device, dtype=torch.float32)
         N.call("dna_onehot_conv_fwd", ids.data_ptr(), w32.data_ptr(), _p(b32), B, L, C, V, KW,
-               int(bool(complement)), N.ACT_GELU, out.data_ptr(), N.stream_ptr())
+               int(bool(complement)), int(act), out.data_ptr(), N.stream_ptr())
         ctx.save_for_backward(ids)
         ctx.params = (w, b)
         ctx.complement = bool(complement)
+        ctx.act = int(act)
         return out
 
     @staticmethod
@@ -2002,13 +2037,14 @@ class OneHotConv(torch.autograd.Function):
         nws = N.lib().dna_onehot_conv_bwd_workspace(B, L, C, V, KW)
         ws = torch.empty(nws, device=ids.device, dtype=torch.uint8)
         N.call("dna_onehot_conv_bwd", ids.data_ptr(), w32.data_ptr(), _p(b32), dout.data_ptr(), B,
-               L, C, V, KW, int(ctx.complement), N.ACT_GELU, dw.data_ptr(), _p(db), int(direct),
+               L, C, V, KW, int(ctx.complement), ctx.act, dw.data_ptr(), _p(db), int(direct),
                ws.data_ptr(), nws, N.stream_ptr())
         if direct:
             _notify_direct(w, b)
-            return None, None, None, None
-        return None, dw, db, None
+            return None, None, None, None, None
+        return None, dw, db, None, None
 
 
-def onehot_conv(ids, weight, bias, complement=False):
-    return OneHotConv.apply(ids, weight, bias, complement)
+def onehot_conv(ids, weight, bias, complement=False, act=N.ACT_GELU):
+    """act: N.ACT_GELU (the fine-tuning forward) | N.ACT_RELU (the pretraining forward's `linear`)."""
+    return OneHotConv.apply(ids, weight, bias, complement, act)

@@ -139,6 +139,14 @@ def random_mask(seq, mask_token_id, mask_prob=0.15):
     return masked, mask
 
 
+def check_objective(objective, use_tokenizer):
+    """`stdmlm_onehot` masks in the one-hot id space (A C G T N = 0..4), which exists only after
+    the use_tokenizer=False remap."""
+    if objective == "stdmlm_onehot" and use_tokenizer:
+        raise ValueError("dataset.objective=stdmlm_onehot masks the one-hot ids A C G T N = 0..4 "
+                         "and needs dataset.use_tokenizer=false")
+
+
 class BertHG38Dataset(torch.utils.data.Dataset):
     """BED rows of one split -> ((masked_ids, mask, labels), target)  (hg38_dataset.py:289-399)."""
 
@@ -157,6 +165,7 @@ class BertHG38Dataset(torch.utils.data.Dataset):
         self.pad_interval = pad_interval
         self.use_tokenizer = use_tokenizer
         self.objective = objective
+        check_objective(objective, use_tokenizer)
         assert os.path.exists(str(bed_file)), "path to .bed file must exist"
         df = pd.read_csv(str(bed_file), sep="\t", names=["chr_name", "start", "end", "split"])
         df = df[df["split"] == split]
@@ -229,6 +238,13 @@ class BertHG38Dataset(torch.utils.data.Dataset):
             seq = torch.where(seq == vocab["N"], torch.full_like(seq, self.tokenizer.pad_token_id), seq)
         data, target = seq.clone(), seq.clone()
         tok = self.tokenizer
+        if self.objective == "stdmlm_onehot":
+            # The reference's rule and draw order in the one-hot id space. Its own recipe
+            # (hg38_bert.yaml, use_tokenizer False) masks the remapped ids with the character
+            # tokenizer's ids instead: a masked base shows as T (3), and the random draws 7..11
+            # are no one-hot class. Here a masked base shows as N (4), random replacements are
+            # A C G T, and N / the end-of-sequence position (both 4) are never masked.
+            return bert_mask(data, 4, 4, 4, special_token_ids=[]), target
         if self.objective == "stdmlm":
             return bert_mask(data, tok.mask_token_id, tok.pad_token_id, tok.vocab_size,
                              special_token_ids=tok.all_special_ids), target
@@ -401,6 +417,7 @@ class BertHG38(FaultTolerantMixin, SequenceDataset):
         self.use_tokenizer = use_tokenizer
         self.pad_max_length = pad_max_length
         self.objective = objective
+        check_objective(objective, use_tokenizer)
         self._init_fault_tolerant(shuffle, fault_tolerant, ddp, fast_forward_epochs,
                                   fast_forward_batches)
         if use_fixed_len_val:

@@ -777,7 +777,8 @@ def lm_head_rc_bwd(coef: torch.Tensor, h: torch.Tensor, w: torch.Tensor, cm: tor
 # ------------------------------------------------------------------------------- dilated conv
 _DCONV_EPI = {"plain": N.DCONV_PLAIN, "gate": N.DCONV_GATE, "main_mul": N.DCONV_MAIN_MUL,
               "main_add": N.DCONV_MAIN_ADD}
-_DCONV_ACT = {"none": N.ACT_NONE, "gelu": N.ACT_GELU, "sigmoid": N.ACT_SIGMOID}
+_DCONV_ACT = {"none": N.ACT_NONE, "gelu": N.ACT_GELU, "sigmoid": N.ACT_SIGMOID,
+              "relu": N.ACT_RELU}  # relu: onehot_conv_* only (dna_dconv_fwd refuses it)
 
 
 def _dconv_x(name, t, like=None):

@@ -172,14 +172,16 @@ def load_pretrained(model, state_dict, freeze_backbone=False):
     from dna_amd.denoise import CNNModel
     if isinstance(model, SequenceClassifier) and isinstance(model.model, CNNModel):
         # denoise_cnn: one of this script's checkpoints (keys model.* and decoder.0.*: everything,
-        # strictly) or a same-key backbone state dict (the reference's; its decoder.* keys are
-        # dropped and the head stays fresh), also strictly
+        # strictly) or a same-key backbone state dict (the reference's, or train.py's masked-LM
+        # checkpoint; its decoder.* and out_linear.* keys are dropped and the head stays fresh),
+        # also strictly
         if freeze_backbone:
             raise NotImplementedError("freeze_backbone is built for dna_embedding only")
         if any(k.startswith("model.") for k in sd):
             model.load_state_dict(sd)
             return {"loaded": "classifier"}
-        model.model.load_state_dict({k: v for k, v in sd.items() if not k.startswith("decoder.")})
+        model.model.load_state_dict({k: v for k, v in sd.items()
+                                     if not k.startswith(("decoder.", "out_linear."))})
         return {"loaded": "backbone", "kept_fresh": ["decoder.0.output_transform"]}
     if isinstance(model, SequenceClassifier):
         if any(k.startswith("decoder.0.") for k in sd):

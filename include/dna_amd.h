@@ -25,8 +25,9 @@ extern "C" {
 #define DNA_AMD_ABI_VERSION 1
 /* Counts additions that leave every version-1 entry point as it was (a caller built against an
  * earlier revision keeps working): 1 = dna_lm_head_*, 2 = dna_lm_head_rc_*, 3 = dna_attn_varlen_*,
- * 4 = dna_dconv_* / dna_onehot_conv_*, 5 = dna_selective_scan_plan. */
-#define DNA_AMD_ABI_REVISION 5
+ * 4 = dna_dconv_* / dna_onehot_conv_*, 5 = dna_selective_scan_plan, 6 = dna_lm_head_bias_* and
+ * DNA_ACT_RELU in dna_onehot_conv_*. */
+#define DNA_AMD_ABI_REVISION 6
 
 enum dna_status {
   DNA_OK = 0,
@@ -38,7 +39,12 @@ enum dna_status {
 };
 
 enum dna_dtype { DNA_F32 = 0, DNA_BF16 = 1, DNA_F16 = 2 };
-enum dna_act { DNA_ACT_NONE = 0, DNA_ACT_GELU = 1, DNA_ACT_SIGMOID = 2 /* dna_dconv_* only */ };
+enum dna_act {
+  DNA_ACT_NONE = 0,
+  DNA_ACT_GELU = 1,
+  DNA_ACT_SIGMOID = 2, /* dna_dconv_* only */
+  DNA_ACT_RELU = 3     /* dna_onehot_conv_* only */
+};
 
 int dna_abi_version(void);
 int dna_abi_revision(void);
@@ -714,6 +720,25 @@ int dna_lm_head_bwd(const float* coef, const void* h, int64_t h_stride, int h_dt
                     int64_t dh_stride, float* dW, int accumulate, void* workspace,
                     size_t workspace_bytes, void* stream);
 
+/* The same head with an untied weight and a bias (the reference's CNNModel.out_linear,
+ * src/models/sequence/denoise.py, pretrain branch): bias [V] fp32 or NULL,
+ *   logit_v = sum_d h[r, d] W[v, d] + bias[v]      (one fp32 add after the row's sum)
+ *   dbias[v] (+)= g sum_r coef[r, v]               (NULL: not computed; needs dW)
+ * dbias is summed from per-chunk partials over the same chunks, in the same row order, as dW's,
+ * and `accumulate` applies to both. Everything else is as above; the kernels are the same, so
+ * bias == NULL (and dbias == NULL) gives dna_lm_head_fwd / dna_lm_head_bwd bit for bit. The
+ * backward's workspace grows by the dbias partials. Backward 1 (dh) + 2 (dW) + 1 (dbias). */
+int dna_lm_head_bias_fwd(const void* h, int64_t h_stride, int h_dtype, const void* W, int w_dtype,
+                         const float* bias, const int64_t* labels, int rows, int width, int vocab,
+                         float denom, float* loss_sum, int64_t* count, float* loss, float* coef,
+                         void* workspace, size_t workspace_bytes, void* stream);
+size_t dna_lm_head_bias_bwd_workspace(int rows, int width, int vocab);
+int dna_lm_head_bias_bwd(const float* coef, const void* h, int64_t h_stride, int h_dtype,
+                         const void* W, int w_dtype, const int64_t* labels, const int64_t* count,
+                         const float* upstream, float denom, int rows, int width, int vocab,
+                         void* dh, int64_t dh_stride, float* dW, float* dbias, int accumulate,
+                         void* workspace, size_t workspace_bytes, void* stream);
+
 /* The RC-equivariant variant (Caduceus RCPSLMHead, reference
  * src/models/caduceus/modeling_rcps.py:206-243): h [T, 2 D] (both strands' channels), the tied
  * W [V, D] and a complement map cm [V] (device int64, entries in [0, V), validated by the caller
@@ -805,8 +830,9 @@ int dna_dconv_wgrad(const void* dz, const void* x, int dtype, int B, int L, int 
  *   out[b, l, co] = act(bias[co] + sum_{t < KW} W[co, id[b, l + t - (KW - 1) / 2], t])
  * ids [B, L] int64 (an id outside [0, V) or a position outside the row adds nothing), W [C, V, KW]
  * and bias [C] fp32, out [B, L, C] fp32. complement != 0 reads 3 - id for id < 4 (A<->T, C<->G; N
- * and anything above stay). V <= 8, KW odd <= 9, C % 64 == 0. The backward recomputes z and
- * writes dw [C, V, KW] and dbias [C] from per-block partials summed in a fixed order. */
+ * and anything above stay). V <= 8, KW odd <= 9, C % 64 == 0. act: DNA_ACT_NONE | DNA_ACT_GELU |
+ * DNA_ACT_SIGMOID | DNA_ACT_RELU (max(z, 0); derivative 0 for z <= 0). The backward recomputes z
+ * and writes dw [C, V, KW] and dbias [C] from per-block partials summed in a fixed order. */
 int dna_onehot_conv_fwd(const int64_t* ids, const float* w, const float* bias, int B, int L, int C,
                         int V, int KW, int complement, int act, float* out, void* stream);
 size_t dna_onehot_conv_bwd_workspace(int B, int L, int C, int V, int KW);

@@ -10,7 +10,9 @@ train() :668-694 -> Lightning fit) for the DNABERT-2 MLM path, without Hydra or 
     the fused small-vocabulary head, `_optim` AdamW groups), model "caduceus" ->
     dna_amd.caduceus.CaduceusForMaskedLM (src/utils/registry.py:37; the same trainer, the
     RC-equivariant fused head for rcps, `train.optimizer_param_grouping` -> no weight decay on
-    A_log / D / biases / embeddings), schedulers "linear_warmup" and "cosine_warmup_timm",
+    A_log / D / biases / embeddings), model "denoise_cnn" -> dna_amd.denoise.CNNModel
+    (src/utils/registry.py:32 with pretrain true: the gated dilated CNN, the same trainer, the
+    biased fused head on the masked rows), schedulers "linear_warmup" and "cosine_warmup_timm",
     dataset "bert_hg38" -> dna_amd.hg38.BertHG38, "dnabert2_pretrain" (text corpus) ->
     dna_amd.corpus.DNABERT2Pretrain, task "hg38" + loss "bert_cross_entropy";
   * loop: MLMTrainer steps (fused loss, bucketed RCCL all-reduce, clip + AdamW, LR schedule per
@@ -52,10 +54,12 @@ from dna_amd.compose import compose  # noqa: E402
 
 MODEL_REGISTRY = {"dnabert2": "dna_amd.bert_layers.BertForMaskedLM",
                   "blm": "dna_amd.hyena_lm.BertLMHeadModel",
-                  "caduceus": "dna_amd.caduceus.CaduceusForMaskedLM"}
+                  "caduceus": "dna_amd.caduceus.CaduceusForMaskedLM",
+                  "denoise_cnn": "dna_amd.denoise.CNNModel"}
 # the step engine that goes with each registry model
 TRAINER_REGISTRY = {"dnabert2": "dna_amd.trainer.MLMTrainer", "blm": "dna_amd.trainer.BlmTrainer",
-                    "caduceus": "dna_amd.trainer.BlmTrainer"}
+                    "caduceus": "dna_amd.trainer.BlmTrainer",
+                    "denoise_cnn": "dna_amd.trainer.BlmTrainer"}
 SCHEDULERS = ("linear_warmup", "cosine_warmup_timm")
 
 
@@ -96,9 +100,9 @@ def on_module_trainer(name):
 def build_model(cfg, precision):
     """The registry model of cfg.model. "dnabert2" and "caduceus" take their `config:` sub-key
     (the one the Caduceus fine-tuning configs use; with rcps set and complement_map null the map
-    comes from the character tokenizer, as in finetune.py); "blm" is built from cfg.model's own
-    keys (the reference's blm block has no `config:`), and keys LMBackbone refuses keep
-    raising."""
+    comes from the character tokenizer, as in finetune.py); "blm" and "denoise_cnn" are built
+    from cfg.model's own keys (the reference's blocks have no `config:`; denoise_cnn's `args:`
+    arrives as a mapping), and keys LMBackbone / CNNModel refuse keep raising."""
     name = cfg.model._name_
     if name not in MODEL_REGISTRY:
         raise KeyError(f"model._name_={name!r} is not in train.py's registry "
