@@ -172,6 +172,8 @@ _SIGS = {
     "dna_sumsq": (_i, [_vp, _sz, _vp, _vp, _sz, _vp]),
     "dna_adamw_step": (_i, [_vp, _vp, _vp, _vp, _vp, _sz, _f, _f, _f, _f, _f, _i, _vp, _f, _f,
                             _vp]),
+    "dna_char_batch": (_i, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i, _i, _i, _i64, _i64, _vp,
+                            _vp, _vp]),
     "dna_bpe_create": (_vp, [ctypes.c_char_p]),
     "dna_bpe_destroy": (None, [_vp]),
     "dna_bpe_vocab_size": (_i, [_vp]),

@@ -3,7 +3,9 @@
 tokenizer as [CLS] ... [SEP], truncated to max_length, padded per batch; and Genomic Benchmarks
 folders (`<dest>/<name>/<split>/<class>/*.txt`, one sequence per file), tokenised per character
 to a fixed length for the HyenaDNA / Caduceus classifiers; and, tokenised the same way, the
-DeepSTARR files (two regression targets per sequence) and the DeepSEA tables (919 0/1 labels)."""
+DeepSTARR files (two regression targets per sequence), the DeepSEA tables (919 0/1 labels) and the
+Nucleotide Transformer benchmark's FASTA files (labels in the headers; NT_TASKS is its task
+table)."""
 import csv
 import gzip
 import os
@@ -150,6 +152,15 @@ class _CharItems(torch.utils.data.Dataset):
             return ids, target, mask
         return ids, target
 
+    def __getitem__(self, idx):
+        return self._item(*self._pair(idx))
+
+    def pairs(self):
+        """(sequence string, target) of every item in order, before rc_aug and tokenisation: what
+        a device-resident copy of the split is made from (resident.ResidentSplit). A loader
+        defines `_pair(idx)`."""
+        return (self._pair(i) for i in range(len(self)))
+
     def collate(self, items):
         """[(ids, target[, mask])] of one fixed length -> stacked tensors, in the same order."""
         return tuple(torch.stack(col) for col in zip(*items))
@@ -206,8 +217,8 @@ class GenomicBenchmarkFolder(_CharItems):
     def __len__(self):
         return len(self.all_labels)
 
-    def __getitem__(self, idx):
-        return self._item(self.all_seqs[idx], torch.tensor(self.all_labels[idx], dtype=torch.int64))
+    def _pair(self, idx):
+        return self.all_seqs[idx], torch.tensor(self.all_labels[idx], dtype=torch.int64)
 
 
 DEEPSTARR_TARGETS = ("Dev_log2_enrichment", "Hk_log2_enrichment")
@@ -278,8 +289,8 @@ class DeepSTARRFolder(_CharItems):
     def __len__(self):
         return len(self.all_seqs)
 
-    def __getitem__(self, idx):
-        return self._item(self.all_seqs[idx], self.targets[idx])
+    def _pair(self, idx):
+        return self.all_seqs[idx], self.targets[idx]
 
 
 DEEPSEA_LABELS = 919
@@ -329,5 +340,122 @@ class DeepSEACsv(_CharItems):
     def __len__(self):
         return len(self.all_seqs)
 
-    def __getitem__(self, idx):
-        return self._item(self.all_seqs[idx], self.labels[idx].to(torch.float32))
+    def _pair(self, idx):
+        return self.all_seqs[idx], self.labels[idx].to(torch.float32)
+
+
+# The Nucleotide Transformer benchmark's 18 tasks: the per-task entries of the reference's
+# configs/dataset/nucleotide_transformer.yaml (tests/golden/nt_tasks.json is parsed from it).
+# train_len: training sequences (the cosine schedule's length); classes: d_output; max_length:
+# the tokenised length; metric: what train.monitor follows as val/<metric>.
+def _nt(train_len, classes, max_length, metric):
+    return {"train_len": train_len, "classes": classes, "max_length": max_length, "metric": metric}
+
+
+NT_TASKS = {
+    "enhancer": _nt(14968, 2, 200, "mcc"),
+    "enhancer_types": _nt(14968, 3, 200, "mcc"),
+    "H3": _nt(13468, 2, 500, "mcc"),
+    "H3K4me1": _nt(28509, 2, 500, "mcc"),
+    "H3K4me2": _nt(27614, 2, 500, "mcc"),
+    "H3K4me3": _nt(33119, 2, 500, "mcc"),
+    "H3K9ac": _nt(25003, 2, 500, "mcc"),
+    "H3K14ac": _nt(29743, 2, 500, "mcc"),
+    "H3K36me3": _nt(31392, 2, 500, "mcc"),
+    "H3K79me3": _nt(25953, 2, 500, "mcc"),
+    "H4": _nt(13140, 2, 500, "mcc"),
+    "H4ac": _nt(30685, 2, 500, "mcc"),
+    "promoter_all": _nt(53276, 2, 300, "f1_macro"),
+    "promoter_non_tata": _nt(47759, 2, 300, "f1_macro"),
+    "promoter_tata": _nt(5517, 2, 300, "f1_macro"),
+    "splice_sites_acceptor": _nt(19961, 2, 600, "f1_macro"),
+    "splice_sites_donor": _nt(19775, 2, 600, "f1_macro"),
+    "splice_sites_all": _nt(27000, 3, 600, "f1_macro"),
+}
+
+
+def read_fasta(path):
+    """-> [(header line after '>', sequence)] of a FASTA file with any line wrapping; blank lines
+    are skipped, sequence lines are joined without their line ends."""
+    records, key, parts = [], None, []
+    with open(path) as f:
+        for line in f:
+            line = line.rstrip("\r\n")
+            if line.startswith(">"):
+                if key is not None:
+                    records.append((key, "".join(parts)))
+                key, parts = line[1:], []
+            elif line.strip():
+                if key is None:
+                    raise ValueError(f"{path}: a sequence before the first header")
+                parts.append(line.strip())
+    if key is not None:
+        records.append((key, "".join(parts)))
+    return records
+
+
+class NucleotideTransformerFasta(_CharItems):
+    """One split of a Nucleotide Transformer benchmark task as the reference's
+    NucleotideTransformerDataset reads it (src/dataloaders/datasets/
+    nucleotide_transformer_dataset.py:26-113): the folder `<dest_path>/<dataset_name>/` holds one
+    `*.fasta` file per split, found by the split's name in the file name; split "val" reads
+    "test" (the benchmark has no validation split). A record's key is its whole header line
+    after '>' (pyfaidx read_long_names) and its label the key's last character, as an integer:
+    `int(key.rstrip()[-1])`. Nothing is ever downloaded: a missing folder or file is an error
+    that says where the files are expected.
+
+    Two deliberate differences from the reference. It tests `split in str(file)` on the whole
+    path, so a parent directory named like a split matches every file and the last one
+    `iterdir()` lists wins; here only the file name is matched, and no match or more than one
+    is an error. Duplicate headers are an error (pyfaidx's default makes them one), and so is a
+    label >= d_output.
+
+    Items are (ids int64 [max_length], label int64) (+ mask); tokenisation, add_eos, rc_aug,
+    return_mask and collate as in _CharItems. use_tokenizer=False (or id_remap=True): the ids of
+    the one-hot models (`remap_ids`)."""
+
+    def __init__(self, dest_path, dataset_name, split, max_length, tokenizer=None, d_output=None,
+                 use_padding=True, add_eos=False, rc_aug=False, return_mask=False, rng=None,
+                 use_tokenizer=True, id_remap=None):
+        self.split = "test" if split == "val" else split
+        self.base_path = os.path.join(str(dest_path), dataset_name)
+        where = (f"Nucleotide Transformer benchmark data is not downloaded here; put the task's "
+                 f"files at <dest_path>/{dataset_name}/*{self.split}*.fasta")
+        if not os.path.isdir(self.base_path):
+            raise FileNotFoundError(f"{self.base_path}: no such folder. {where}")
+        found = sorted(fn for fn in os.listdir(self.base_path)
+                       if fn.endswith(".fasta") and self.split in fn)
+        if not found:
+            raise FileNotFoundError(f"{self.base_path}: no *.fasta file named after the split "
+                                    f"{self.split!r}. {where}")
+        if len(found) > 1:
+            raise ValueError(f"{self.base_path}: {found} all match the split {self.split!r}; "
+                             "exactly one *.fasta file per split is expected")
+        self.path = os.path.join(self.base_path, found[0])
+        self._init_items(max_length, tokenizer, use_padding, add_eos, rc_aug, return_mask, rng,
+                         _want_remap(use_tokenizer, id_remap))
+        known = NT_TASKS.get(dataset_name)
+        self.d_output = int(d_output) if d_output is not None else (known["classes"] if known
+                                                                    else None)
+        self.all_seqs, self.all_labels, seen = [], [], set()
+        for key, seq in read_fasta(self.path):
+            if key in seen:
+                raise ValueError(f"{self.path}: duplicate header {key!r}")
+            seen.add(key)
+            last = key.rstrip()[-1:]
+            if not last.isdigit():
+                raise ValueError(f"{self.path}: header {key!r} does not end in a label digit")
+            label = int(last)
+            if self.d_output is not None and label >= self.d_output:
+                raise ValueError(f"{self.path}: header {key!r} has label {label}, but d_output "
+                                 f"is {self.d_output}")
+            self.all_seqs.append(seq)
+            self.all_labels.append(label)
+        self.num_labels = (self.d_output if self.d_output is not None
+                           else max(self.all_labels, default=-1) + 1)
+
+    def __len__(self):
+        return len(self.all_labels)
+
+    def _pair(self, idx):
+        return self.all_seqs[idx], torch.tensor(self.all_labels[idx], dtype=torch.int64)

@@ -210,6 +210,9 @@ POOL_LOSSES = {
 # task._name_ -> the problem type its losses must have and its default loss
 POOL_TASKS = {
     "sequence_classification": ("single_label_classification", "cross_entropy"),
+    # the reference's Nucleotide Transformer experiments name their task masked_multiclass; with
+    # one label per sequence and cross_entropy it is the single-label task above
+    "masked_multiclass": ("single_label_classification", "cross_entropy"),
     "regression": ("regression", "mse"),
     "multilabel_classification": ("multi_label_classification", "binary_cross_entropy"),
 }

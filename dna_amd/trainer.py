@@ -255,14 +255,23 @@ def load_backbone(model, path, strict=False):
 
 class _ClsSteps(ModuleTrainer):
     """What the two fine-tuning trainers share: a model with `cls_logits(input_ids, labels) ->
-    (logits, loss, pred)`, step(input_ids, labels), last_logits / last_pred, evaluate, a linear
-    warmup schedule. Single GPU (multi-rank fine-tuning is not built)."""
+    (logits, loss, pred)`, step(input_ids, labels), last_logits / last_pred, evaluate, a
+    schedule (scheduler_name: linear_warmup, or cosine_warmup_timm with optim's refusals). Single
+    GPU (multi-rank fine-tuning is not built)."""
 
-    def __init__(self, model, device, scheduler, **kw):
+    def __init__(self, model, device, scheduler, scheduler_name="linear_warmup", **kw):
+        if scheduler_name not in SCHEDULERS:
+            raise NotImplementedError(f"scheduler {scheduler_name!r}: one of {sorted(SCHEDULERS)}")
         super().__init__(model, device, self._cls_loss, **kw)
-        self.sched = LinearLRSchedulerWarmup(self.opt, **scheduler) if scheduler else None
+        self.sched = self._make_sched(self.opt, scheduler, scheduler_name)
         self.last_logits = None
         self.last_pred = None
+
+    @staticmethod
+    def _make_sched(opt, scheduler, scheduler_name="linear_warmup"):
+        """The schedule the constructor attaches to its optimizer: `scheduler` (keyword
+        arguments, None: no schedule) on the class `scheduler_name` names in optim.SCHEDULERS."""
+        return SCHEDULERS[scheduler_name](opt, **scheduler) if scheduler else None
 
     def _cls_loss(self, model, batch):
         input_ids, labels, packed = batch
@@ -302,9 +311,11 @@ class ClsTrainer(_DropoutStreamState, _ClsSteps):
     dropout-stream state for checkpoints. Single GPU."""
 
     def __init__(self, model: BertForSequenceClassification, device, lr=3e-5, weight_decay=0.01,
-                 betas=(0.9, 0.999), eps=1e-8, max_grad_norm=1.0, scheduler=None, seed=None):
+                 betas=(0.9, 0.999), eps=1e-8, max_grad_norm=1.0, scheduler=None, seed=None,
+                 scheduler_name="linear_warmup"):
         _single_gpu_only("ClsTrainer")
-        super().__init__(model, device, scheduler, lr=lr, weight_decay=weight_decay, betas=betas,
+        super().__init__(model, device, scheduler, scheduler_name, lr=lr,
+                         weight_decay=weight_decay, betas=betas,
                          eps=eps, max_grad_norm=max_grad_norm, autocast=None, lp_tags=False)
         self._seed_stream(seed)
 
@@ -322,15 +333,20 @@ class SeqClsTrainer(_TorchGeneratorState, _ClsSteps):
     # at max(lr, initial_lr) of group 0: while the schedule stays at or under the base lr the order
     # makes no difference, but one that goes over it (warmup_lr_init or lr_min above lr,
     # cycle_decay > 1, all of which finetune.py passes on from the config) hands the check another
-    # lr in the other order, and with it possibly another LayerNorm backward path.
+    # lr in the other order, and with it possibly another LayerNorm backward path. The same holds
+    # for cosine_warmup_timm: warmup rises from warmup_lr_init to the base lr, the cosine falls
+    # from it to lr_min, so with warmup_lr_init and lr_min at or under lr (the Nucleotide
+    # Transformer experiments: 1e-6 and 0.1 lr) it never exceeds the base lr either.
     _sched_before_guard = False
 
     def __init__(self, model, device, lr=6e-4, weight_decay=0.1, betas=(0.9, 0.999), eps=1e-8,
-                 max_grad_norm=1.0, scheduler=None, seed=None, autocast=torch.bfloat16):
+                 max_grad_norm=1.0, scheduler=None, seed=None, autocast=torch.bfloat16,
+                 scheduler_name="linear_warmup"):
         _single_gpu_only("SeqClsTrainer")
         if seed is not None:
             torch.manual_seed(int(seed) + 0x5EED)
-        super().__init__(model, device, scheduler, lr=lr, weight_decay=weight_decay, betas=betas,
+        super().__init__(model, device, scheduler, scheduler_name, lr=lr,
+                         weight_decay=weight_decay, betas=betas,
                          eps=eps, max_grad_norm=max_grad_norm, autocast=autocast)
         self.opt.numel = self._trainable_extent()
 

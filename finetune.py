@@ -32,6 +32,17 @@ their own train / val / test files:
     python finetune.py experiment=hyena/deepsea_hyena dataset.dest_path=/data/deepsea
     python finetune.py experiment=caduceus/deepstarr_caduceus dataset.dest_path=/data/deepstarr
 
+dataset._name_ nucleotide_transformer reads one task of the Nucleotide Transformer benchmark
+(<dest_path>/<dataset_name>/*train*.fasta and *test*.fasta, labels in the headers; val and test
+are both the test file); length, labels, schedule length and the monitored metric come from the
+task table (finetune_data.NT_TASKS) unless given, with the cosine_warmup_timm schedule:
+
+    python finetune.py experiment=hyena/nt_hyena dataset.dest_path=/data/nt dataset.dataset_name=H3
+
+dataset.resident=true (the pooling models; every dataset above) keeps the splits on the device and
+builds each batch there with one HIP kernel (dna_amd.resident), bit-identical to the item-by-item
+path for the same seeds.
+
 train.pretrained_model_path there takes an LM / masked-LM checkpoint of train.py (backbone
 loaded, head fresh; dna_embedding honours train.pretrained_model_state_hook.freeze_backbone: the
 backbone then gets no update and no weight decay) or one of this script's checkpoints.
@@ -58,12 +69,65 @@ def _model_config(cfg, num_labels=None):
     return mc
 
 
+FT_SCHEDULERS = ("linear_warmup", "cosine_warmup_timm")
+
+
+def _scheduler_name(cfg):
+    if "scheduler" not in cfg or cfg.scheduler is None:
+        return "linear_warmup"
+    return cfg.scheduler._name_
+
+
 def _scheduler(cfg):
+    """-> the scheduler's keyword arguments (its class: _scheduler_name). cosine_warmup_timm with
+    t_initial, warmup_t or lr_min null takes them as the reference's Nucleotide Transformer
+    experiments compute them: t_initial = ceil(dataset.train_len / dataset.batch_size) *
+    trainer.max_epochs, warmup_t = 1 % of t_initial, lr_min = 0.1 * optimizer.lr."""
     if "scheduler" not in cfg or cfg.scheduler is None:
         return None
-    if cfg.scheduler._name_ != "linear_warmup":
-        raise NotImplementedError(f"scheduler {cfg.scheduler._name_!r} (linear_warmup only)")
-    return {k: v for k, v in cfg.scheduler.to_container().items() if k != "_name_"}
+    if cfg.scheduler._name_ not in FT_SCHEDULERS:
+        raise NotImplementedError(f"scheduler {cfg.scheduler._name_!r} (one of {FT_SCHEDULERS})")
+    sched = {k: v for k, v in cfg.scheduler.to_container().items() if k != "_name_"}
+    if cfg.scheduler._name_ == "cosine_warmup_timm":
+        if sched.get("t_initial") is None or sched.get("warmup_t") is None:
+            train_len = cfg.dataset.get("train_len")
+            if train_len is None:
+                raise ValueError("scheduler.t_initial / warmup_t are null: dataset.train_len (the "
+                                 "number of training sequences) is needed to compute them")
+            steps = -(-int(train_len) // int(cfg.dataset.get("batch_size", 32)))
+            run = steps * int(cfg.trainer.get("max_epochs", 1))
+            if sched.get("t_initial") is None:
+                sched["t_initial"] = run
+            if sched.get("warmup_t") is None:
+                sched["warmup_t"] = run * 0.01
+        if sched.get("lr_min") is None:
+            sched["lr_min"] = 0.1 * float(cfg.optimizer.get("lr", 6e-4))
+    return sched
+
+
+def _nt_defaults(cfg):
+    """dataset._name_ nucleotide_transformer: max_length, d_output, train_len and metric left
+    null come from finetune_data.NT_TASKS by dataset.dataset_name (explicit values win), and a
+    null train.monitor follows the task's metric as val/<metric>, mode max. Idempotent."""
+    ds = cfg.get("dataset")
+    if ds is None or ds.get("_name_") != "nucleotide_transformer":
+        return
+    from dna_amd.finetune_data import NT_TASKS
+    keys = {"max_length": "max_length", "d_output": "classes", "train_len": "train_len",
+            "metric": "metric"}
+    if any(ds.get(k) is None for k in keys):
+        task = NT_TASKS.get(ds.get("dataset_name"))
+        if task is None:
+            raise ValueError(f"dataset.dataset_name={ds.get('dataset_name')!r}: not one of the "
+                             f"Nucleotide Transformer tasks {sorted(NT_TASKS)}; set "
+                             "dataset.max_length, d_output, train_len and metric yourself")
+        for k, src in keys.items():
+            if ds.get(k) is None:
+                ds[k] = task[src]
+    if cfg.train.get("monitor") is None:
+        cfg.train["monitor"] = f"val/{ds.metric}"
+    if cfg.train.get("mode") is None:
+        cfg.train["mode"] = "max"
 
 
 def _metric(problem_type, num_labels):
@@ -83,20 +147,26 @@ def _metric(problem_type, num_labels):
 def evaluate(trainer, ds, batch_size, device, num_labels,
              problem_type="single_label_classification", unpad=False):
     """-> {"loss", ...the problem type's metrics (_metric)} of one split; the metric's state
-    stays on the device until the split is done. unpad: packed batches (dataset.unpad)."""
+    stays on the device until the split is done. unpad: packed batches (dataset.unpad). A
+    resident.ResidentSplit builds its batches on the device, in the split's own order."""
+    from dna_amd.resident import ResidentSplit
     metric, on_logits = _metric(problem_type, num_labels)
     total = torch.zeros((), device=device, dtype=torch.float64)
+    resident = isinstance(ds, ResidentSplit)
     for i in range(0, len(ds), batch_size):
-        items = [ds[j] for j in range(i, min(i + batch_size, len(ds)))]
-        if unpad:
-            ids, labels, packed = ds.collate(items, unpad=True)
-            packed = packed.to(device)
+        if resident:
+            (ids, labels), packed = ds.batch(i, i + batch_size)[:2], None
         else:
-            (ids, labels), packed = ds.collate(items), None
-        ids, labels = ids.to(device), labels.to(device)
+            items = [ds[j] for j in range(i, min(i + batch_size, len(ds)))]
+            if unpad:
+                ids, labels, packed = ds.collate(items, unpad=True)
+                packed = packed.to(device)
+            else:
+                (ids, labels), packed = ds.collate(items), None
+            ids, labels = ids.to(device), labels.to(device)
         logits, loss, pred = (trainer.evaluate(ids, labels, packed=packed) if unpad
                               else trainer.evaluate(ids, labels))
-        total += loss.double() * len(items)
+        total += loss.double() * ids.shape[0]
         metric.update(logits if on_logits else pred, labels)
     out = metric.compute()
     out["loss"] = (total / max(len(ds), 1)).item()
@@ -195,13 +265,13 @@ def load_pretrained(model, state_dict, freeze_backbone=False):
     return {"missing": list(missing), "unexpected": len(unexpected)}
 
 
-POOL_DATASETS = ("genomic_benchmark", "deepstarr", "deepsea")
+POOL_DATASETS = ("genomic_benchmark", "deepstarr", "deepsea", "nucleotide_transformer")
 
 
 def _pool_splits(ds, tok, max_length):
     """dataset._name_ -> {"train", "dev", "test": dataset}. Genomic Benchmarks have no validation
     split (dev is the test folder); DeepSTARR and DeepSEA have their own train / val / test
-    files."""
+    files; the Nucleotide Transformer benchmark has no validation split either."""
     from dna_amd import finetune_data as FD
     # dataset.use_tokenizer=false (the one-hot models): ids A C G T N = 0..4 (finetune_data.remap_ids)
     kw = dict(max_length=max_length, tokenizer=tok, use_padding=ds.get("use_padding", True),
@@ -213,6 +283,11 @@ def _pool_splits(ds, tok, max_length):
         test_ds = FD.GenomicBenchmarkFolder(ds.dest_path, ds.dataset_name, "val",
                                             classes=train_ds.classes, **kw)
         return {"train": train_ds, "dev": test_ds, "test": test_ds}
+    if name == "nucleotide_transformer":
+        make = lambda split, **k: FD.NucleotideTransformerFasta(
+            ds.dest_path, ds.dataset_name, split, d_output=ds.get("d_output"), **kw, **k)
+        test_ds = make("val")
+        return {"train": make("train", rc_aug=rc), "dev": test_ds, "test": test_ds}
     if name == "deepstarr":
         make = lambda split, **k: FD.DeepSTARRFolder(ds.dest_path, split, **kw, **k)
     else:
@@ -232,11 +307,16 @@ def finetune_pool(cfg, dry_run=False, out=sys.stdout):
     if seed is not None:
         torch.manual_seed(int(seed))
     precision = T._precision(cfg.trainer.get("precision", "bf16"))
-    sched = _scheduler(cfg)
-    opt = cfg.optimizer.to_container()
     ds = cfg.dataset
     if ds.get("_name_", "genomic_benchmark") not in POOL_DATASETS:
         raise ValueError(f"dataset._name_={ds.get('_name_')!r}: one of {POOL_DATASETS}")
+    _nt_defaults(cfg)
+    sched = _scheduler(cfg)
+    opt = cfg.optimizer.to_container()
+    resident = bool(ds.get("resident", False))
+    if resident and not ds.get("use_padding", True):
+        raise ValueError("dataset.resident=true with dataset.use_padding=false: ragged items have "
+                         "no fixed length, a resident split builds rectangles only")
     max_length = int(ds.get("max_length", 200))
     if ds.get("unpad", False):
         raise ValueError(f"dataset.unpad=true: model._name_={cfg.model._name_!r} has no packed "
@@ -249,7 +329,8 @@ def finetune_pool(cfg, dry_run=False, out=sys.stdout):
                           "num_labels": model.num_labels, "problem_type": model.problem_type,
                           "loss_scale": model.loss_scale, "dataset": ds.get("_name_"),
                           "dest_path": ds.get("dest_path"),
-                          "dataset_name": ds.get("dataset_name"),
+                          "dataset_name": ds.get("dataset_name"), "max_length": max_length,
+                          "resident": resident, "scheduler_name": _scheduler_name(cfg),
                           "monitor": cfg.train.monitor, "mode": cfg.train.mode,
                           "scheduler": sched, "optimizer": opt}), file=out)
         return None
@@ -275,8 +356,17 @@ def finetune_pool(cfg, dry_run=False, out=sys.stdout):
                             betas=tuple(opt.get("betas", (0.9, 0.999))),
                             eps=float(opt.get("eps", 1e-8)),
                             max_grad_norm=cfg.trainer.get("gradient_clip_val", 1.0),
-                            scheduler=sched, seed=seed,
+                            scheduler=sched, scheduler_name=_scheduler_name(cfg), seed=seed,
                             autocast=torch.bfloat16 if precision == "bf16" else None)
+    if resident:
+        # each split once (dev and test may be one dataset): bytes, offsets and targets go to the
+        # device here, and _fit / evaluate take their batches from there
+        from dna_amd.resident import ResidentSplit
+        made = {}
+        for name, split in list(splits.items()):
+            if id(split) not in made:
+                made[id(split)] = ResidentSplit.from_dataset(split, device)
+            splits[name] = made[id(split)]
     return _fit(cfg, trainer, model, splits, device, out)
 
 
@@ -302,6 +392,11 @@ def finetune(cfg, dry_run=False, out=sys.stdout):
             f"model.config.problem_type={problem!r}: finetune.py reads integer labels and reports "
             "accuracy / MCC / F1 from the argmax, i.e. single_label_classification; regression "
             "and multi-label heads train through ClsTrainer directly")
+    if cfg.dataset.get("resident", False):
+        raise ValueError("dataset.resident=true: dnabert2_cls reads BPE tokens of a GUE CSV, "
+                         "padded per batch or packed (dataset.unpad); a resident split holds one "
+                         "byte per character token at a fixed length, for the pooling models "
+                         + ", ".join(POOL_MODELS))
     precision = T._precision(cfg.trainer.get("precision", "bf16"))
     sched = _scheduler(cfg)
     opt = cfg.optimizer.to_container()
@@ -336,7 +431,7 @@ def finetune(cfg, dry_run=False, out=sys.stdout):
                          weight_decay=float(opt.get("weight_decay", 0.01)),
                          betas=tuple(opt.get("betas", (0.9, 0.999))), eps=float(opt.get("eps", 1e-8)),
                          max_grad_norm=cfg.trainer.get("gradient_clip_val", 1.0), scheduler=sched,
-                         seed=seed)
+                         scheduler_name=_scheduler_name(cfg), seed=seed)
     return _fit(cfg, trainer, model, splits, device, out)
 
 
@@ -356,6 +451,8 @@ def _fit(cfg, trainer, model, splits, device, out):
     log_every = int(cfg.trainer.get("log_every_n_steps", 10))
     max_steps = cfg.train.get("max_steps")
     unpad = bool(cfg.dataset.get("unpad", False))  # packed batches: no kernel runs on [PAD] rows
+    from dna_amd.resident import ResidentSplit
+    resident = isinstance(train_ds, ResidentSplit)
     gen = torch.Generator().manual_seed(int(cfg.train.get("seed") or 0))
     print(json.dumps({"event": "start", "train": len(train_ds), "dev": len(splits["dev"]),
                       "test": len(splits["test"]), "num_labels": model.num_labels,
@@ -363,15 +460,21 @@ def _fit(cfg, trainer, model, splits, device, out):
     metrics = {}
     for epoch in range(int(cfg.trainer.get("max_epochs", 1))):
         order = (torch.randperm(len(train_ds), generator=gen) if cfg.dataset.get("shuffle", True)
-                 else torch.arange(len(train_ds))).tolist()
+                 else torch.arange(len(train_ds)))
+        if resident:
+            train_ds.set_epoch(order)  # one upload; the rc_aug flags are drawn here, in order
+        order = order.tolist()
         for i in range(0, len(order), bs):
-            items = [train_ds[j] for j in order[i:i + bs]]
-            if unpad:
+            if resident:
+                loss = trainer.step(*train_ds.batch(i, i + bs)[:2])
+            elif unpad:
+                items = [train_ds[j] for j in order[i:i + bs]]
                 ids, labels, packed = train_ds.collate(items, unpad=True)
                 loss = trainer.step(ids.to(device, non_blocking=True),
                                     labels.to(device, non_blocking=True),
                                     packed=packed.to(device, non_blocking=True))
             else:
+                items = [train_ds[j] for j in order[i:i + bs]]
                 ids, labels = train_ds.collate(items)
                 loss = trainer.step(ids.to(device, non_blocking=True),
                                     labels.to(device, non_blocking=True))
@@ -414,6 +517,7 @@ def main(argv=None):
     if not any(o.startswith("experiment=") for o in overrides):
         overrides.insert(0, "experiment=" + EXPERIMENT)
     cfg = compose(a.config_dir, a.config_name, overrides)
+    _nt_defaults(cfg)
     if a.print_config or a.dry_run:
         print(json.dumps(cfg.to_container(skip_errors=True), indent=1, default=str))
     return finetune(cfg, dry_run=a.dry_run)

@@ -26,8 +26,8 @@ extern "C" {
 /* Counts additions that leave every version-1 entry point as it was (a caller built against an
  * earlier revision keeps working): 1 = dna_lm_head_*, 2 = dna_lm_head_rc_*, 3 = dna_attn_varlen_*,
  * 4 = dna_dconv_* / dna_onehot_conv_*, 5 = dna_selective_scan_plan, 6 = dna_lm_head_bias_* and
- * DNA_ACT_RELU in dna_onehot_conv_*. */
-#define DNA_AMD_ABI_REVISION 6
+ * DNA_ACT_RELU in dna_onehot_conv_*, 7 = dna_char_batch. */
+#define DNA_AMD_ABI_REVISION 7
 
 enum dna_status {
   DNA_OK = 0,
@@ -840,6 +840,21 @@ int dna_onehot_conv_bwd(const int64_t* ids, const float* w, const float* bias, c
                         int B, int L, int C, int V, int KW, int complement, int act, float* dw,
                         float* dbias, int accumulate, void* workspace, size_t workspace_bytes,
                         void* stream);
+
+/* ------------------------------------------------------------------ resident splits
+ * One batch of character tokens from a device-resident split (csrc/char_batch.hip): `bases` holds
+ * the split's sequences, one byte per character, concatenated; offsets [n_seqs + 1]. Row r of the
+ * batch is sequence idx[r] (int64 [B], on the device): keep = min(n, L - eos) tokens
+ * lut[bases[off + j]] -- with rc[r] != 0 (rc may be NULL) lut[comp[bases[off + n - 1 - j]]], the
+ * reverse complement truncated like the forward strand --, then eos_id when it is >= 0, and
+ * pad_id on the remaining cells, on the left (pad_left != 0) or the right. lut int64 [256], comp
+ * uint8 [256]. ids int64 [B, L]; mask (uint8 / bool [B, L], may be NULL) is 0 exactly on the pad
+ * cells. A row whose idx or offsets fall outside the split is written as padding; nothing
+ * outside bases[off .. off + n) is read. */
+int dna_char_batch(const uint8_t* bases, int64_t n_bases, const int64_t* offsets, int64_t n_seqs,
+                   const int64_t* idx, const uint8_t* rc, const int64_t* lut, const uint8_t* comp,
+                   int B, int L, int pad_left, int64_t pad_id, int64_t eos_id, int64_t* ids,
+                   uint8_t* mask, void* stream);
 
 /* ------------------------------------------------------------------ data path (host, C++)
  * BPE tokenizer: bit-exact with the reference's HF `tokenizers` BPE for
