@@ -174,6 +174,7 @@ _SIGS = {
                             _vp]),
     "dna_char_batch": (_i, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i, _i, _i, _i64, _i64, _vp,
                             _vp, _vp]),
+    "dna_genome_windows": (_i, [_vp, _i64, _vp, _vp, _vp, _vp, _i, _i, _i64, _i64, _vp, _vp]),
     "dna_bpe_create": (_vp, [ctypes.c_char_p]),
     "dna_bpe_destroy": (None, [_vp]),
     "dna_bpe_vocab_size": (_i, [_vp]),

@@ -459,3 +459,340 @@ class NucleotideTransformerFasta(_CharItems):
 
     def _pair(self, idx):
         return self.all_seqs[idx], torch.tensor(self.all_labels[idx], dtype=torch.int64)
+
+
+# ------------------------------------------------------------------ windows cut out of genomes
+# The chromosomes of each split of the species benchmark: the reference's table
+# (species_dataset.py SPECIES_CHROMOSOME_SPLITS; tests/golden/species_splits.json is dumped from
+# it) restated. Validation and test chromosomes are the same for all ten species; the training
+# chromosomes are the even ones up to 8, then 14 up to the species' last autosome, then the sex
+# chromosomes it has (the great apes' chromosome 2 is 2A and 2B).
+_SPECIES_VALID = ["1", "3", "12", "13"]
+_SPECIES_TEST = ["5", "7", "9", "10", "11"]
+
+
+def _species_train(last, sex, two=("2",)):
+    return list(two) + ["4", "6", "8"] + [str(i) for i in range(14, last + 1)] + list(sex)
+
+
+SPECIES_SPLITS = {
+    name: {"train": train, "valid": list(_SPECIES_VALID), "test": list(_SPECIES_TEST)}
+    for name, train in {
+        "human": _species_train(22, "XY"),
+        "lemur": _species_train(27, "XY"),
+        "goat": _species_train(29, "XY"),
+        "sheep": _species_train(26, "XY"),
+        "pig": _species_train(18, "XY"),
+        "mouse": _species_train(19, "X"),
+        "gorilla": _species_train(22, "XY", ("2A", "2B")),
+        "orangutan": _species_train(22, "XY", ("2A", "2B")),
+        "chimpanzee": _species_train(22, "XY", ("2A", "2B")),
+        "hippo": _species_train(17, "X"),
+    }.items()
+}
+
+
+def species_split_sizes(total_size, max_length, max_length_val=None, max_length_test=None):
+    """-> {"train", "valid", "test": (items, max_length)} as the reference's Species data module
+    sizes its splits (genomics.py:584-602): total_size * ((max_length_test + 2) // max_len) items
+    for train and valid, total_size for test."""
+    mv = max_length if max_length_val is None else max_length_val
+    mt = max_length if max_length_test is None else max_length_test
+    return {"train": (int(total_size) * ((mt + 2) // max_length), int(max_length)),
+            "valid": (int(total_size) * ((mt + 2) // mv), int(mv)),
+            "test": (int(total_size), int(mt))}
+
+
+class SpeciesWindows(torch.utils.data.Dataset):
+    """One split of the long-range species classification benchmark as the reference's
+    SpeciesDataset makes it (src/dataloaders/datasets/species_dataset.py:82-333, tokenizer_name
+    char): every access draws a random window of a random chromosome of a random species, and the
+    target is the species' index. Files are `<species_dir>/<species>/chr<name>.{fna,fa,fna.gz}`
+    (a .gz is read in memory, never unzipped into the folder), one record each, upper-cased; the
+    chromosomes of `split` (train | valid | test; "val" reads valid) come from SPECIES_SPLITS.
+
+    Per item `rng` (a random.Random; the reference draws from the global one) is asked, in this
+    order, for rng.choices(species, species_weights), rng.choices(chromosomes, weights) and
+    rng.randint(left, right), where with remove_tail_ends left, right = int(len * cutoff),
+    int(len * (1 - cutoff)) (cutoff_train for train, cutoff_test otherwise) and without it
+    left, right = 0, len - max_length -- a chromosome shorter than max_length raises there, as
+    randint does. The window is chrom[start : min(start + max_length, right)], right-justified
+    to max_length with N. That keeps a quirk of the reference: `right` bounds the slice too, so
+    the last max_length bases of a chromosome are never read and rows can be partly or wholly N.
+    The ids are the character ids, [SEP] appended with add_eos, then the last id dropped:
+    max_length ids with add_eos, max_length - 1 without. The index of an access is ignored.
+
+    species_weights / chromosome_weights: "uniform", "weighted_by_bp" (by record length,
+    normalised) or explicit -- a list per species, {species: list} for the chromosomes.
+    weighted_by_bp restates the reference's `len(Fasta)`-based weights from the record lengths;
+    no fixture pins it, since pyfaidx is not available to run the reference's version.
+    task: species_classification only. use_tokenizer=False (or id_remap=True): `remap_ids`.
+
+    `store` is a genome.GenomeStore of this split's chromosomes under "<species>/chr<name>";
+    rows(k) draws k windows as (src, n, left, targets) for resident.ResidentWindows, consuming
+    the rng exactly as k accesses do."""
+
+    redraws = True  # a pass over the split draws new windows
+
+    def __init__(self, species, species_dir, split, max_length, total_size, tokenizer=None,
+                 add_eos=True, species_weights="uniform", chromosome_weights="uniform",
+                 task="species_classification", remove_tail_ends=False, cutoff_train=0.1,
+                 cutoff_test=0.2, rng=None, use_tokenizer=True, id_remap=None):
+        from .genome import GenomeStore
+        if task == "next_token_pred":
+            raise NotImplementedError("SpeciesWindows task=next_token_pred is not built; "
+                                      "species_classification only")
+        if task != "species_classification":
+            raise ValueError(f"task {task!r}: species_classification")
+        self.split = "valid" if split == "val" else split
+        if self.split not in ("train", "valid", "test"):
+            raise ValueError(f"split {split!r}: one of train, val / valid, test")
+        self.species = list(species)
+        self.max_length, self.total_size = int(max_length), int(total_size)
+        self.add_eos = bool(add_eos)
+        self.row_length = self.max_length if self.add_eos else self.max_length - 1
+        if self.row_length < 1:
+            raise ValueError(f"max_length {max_length}: no id is left after the last is dropped")
+        self.tokenizer = tokenizer or CharacterTokenizer(["A", "C", "G", "T", "N"],
+                                                         self.max_length + 2)
+        self.id_remap = _want_remap(use_tokenizer, id_remap)
+        self.rng = rng or random.Random()
+        self.remove_tail_ends = bool(remove_tail_ends)
+        self.cutoff = float(cutoff_train if self.split == "train" else cutoff_test)
+        self.num_labels = self.d_output = len(self.species)
+        records, self.chromosomes = {}, {}
+        for spec in self.species:
+            if spec not in SPECIES_SPLITS:
+                raise ValueError(f"species {spec!r}: one of {sorted(SPECIES_SPLITS)}")
+            folder = os.path.join(str(species_dir), spec)
+            if not os.path.isdir(folder):
+                raise FileNotFoundError(f"{folder}: no such folder. Genomes are not downloaded "
+                                        "here; put chr<name>.fna (.fa, .fna.gz) files there")
+            self.chromosomes[spec] = list(SPECIES_SPLITS[spec][self.split])
+            for chrom in self.chromosomes[spec]:
+                path = GenomeStore.find(folder, f"chr{chrom}")
+                recs = GenomeStore.from_fasta(path, upper=True)
+                if len(recs) != 1:
+                    raise ValueError(f"{path}: {len(recs)} records, one chromosome is expected")
+                records[f"{spec}/chr{chrom}"] = recs.record(recs.names[0])
+        self.store = GenomeStore(records)
+        lens = {s: [self.store.length(f"{s}/chr{c}") for c in self.chromosomes[s]]
+                for s in self.species}
+        norm = lambda w: [x / sum(w) for x in w]
+        self.chromosome_weights = {}
+        for spec in self.species:
+            w = (chromosome_weights.get(spec) if isinstance(chromosome_weights, dict)
+                 else chromosome_weights)
+            if w == "uniform":
+                w = [1] * len(lens[spec])
+            elif w == "weighted_by_bp":
+                w = norm(lens[spec])
+            elif not isinstance(w, (list, tuple)) or len(w) != len(lens[spec]):
+                raise ValueError(f"chromosome_weights for {spec!r}: uniform, weighted_by_bp or "
+                                 f"{len(lens[spec])} weights, one per chromosome of the split")
+            self.chromosome_weights[spec] = list(w)
+        if species_weights == "uniform":
+            self.species_weights = [1] * len(self.species)
+        elif species_weights == "weighted_by_bp":
+            self.species_weights = norm([sum(lens[s]) for s in self.species])
+        elif isinstance(species_weights, (list, tuple)) and len(species_weights) == len(self.species):
+            self.species_weights = list(species_weights)
+        else:
+            raise ValueError(f"species_weights: uniform, weighted_by_bp or {len(self.species)} "
+                             "weights, one per species")
+
+    def __len__(self):
+        return self.total_size
+
+    def draw(self):
+        """One window: (species index, record name, start, bases read), three draws."""
+        spec = self.rng.choices(self.species, weights=self.species_weights, k=1)[0]
+        chrom = self.rng.choices(self.chromosomes[spec], weights=self.chromosome_weights[spec],
+                                 k=1)[0]
+        name = f"{spec}/chr{chrom}"
+        length = self.store.length(name)
+        if self.remove_tail_ends:
+            left, right = int(length * self.cutoff), int(length * (1 - self.cutoff))
+        else:
+            left, right = 0, length - self.max_length
+        start = self.rng.randint(left, right)
+        return self.species.index(spec), name, start, min(start + self.max_length, right) - start
+
+    def __getitem__(self, idx):
+        label, name, start, n = self.draw()
+        seq = self.store.record(name)[start:start + n].decode("latin-1").rjust(self.max_length, "N")
+        ids = self.tokenizer(seq, add_special_tokens=False)["input_ids"]
+        if self.add_eos:
+            ids.append(self.tokenizer.sep_token_id)
+        ids = torch.tensor(ids, dtype=torch.int64)[:-1].clone()
+        if self.id_remap:
+            ids = remap_ids(ids)
+        return ids, torch.tensor(label, dtype=torch.int64)
+
+    def rows(self, k):
+        """k windows as the device kernel takes them -> (src int64 [k], n int32 [k], left int32
+        [k], targets int64 [k]): the same draws, in the same order, as k accesses."""
+        src, n, tgt = torch.empty(k, dtype=torch.int64), torch.empty(k, dtype=torch.int32), \
+            torch.empty(k, dtype=torch.int64)
+        for i in range(k):
+            label, name, start, nb = self.draw()
+            src[i], n[i], tgt[i] = self.store.offset(name) + start, nb, label
+        return src, n, self.max_length - n, tgt
+
+    def window_spec(self):
+        """How a row is filled: (byte -> id table int64 [256], fill id, eos id or -1, tail id or
+        -1). The fill is N's id; the [SEP] of add_eos is the id that is dropped."""
+        lut = torch.from_numpy(self.tokenizer._lut.astype("int64").copy())
+        fill = torch.tensor(int(lut[ord("N")]))
+        if self.id_remap:
+            lut, fill = remap_ids(lut), remap_ids(fill)
+        return lut, int(fill), -1, -1
+
+    def collate(self, items):
+        return tuple(torch.stack(col) for col in zip(*items))
+
+
+class ChromatinProfile(torch.utils.data.Dataset):
+    """One split of the chromatin-profile benchmark as the reference's ChromatinProfileDataset
+    reads it (src/dataloaders/datasets/chromatin_profile_dataset.py:30-224, genomics.py:420-494):
+    `<data_path>/<split>_<ref_genome_version>_coords_targets.csv` (split train | val | test) with
+    the columns Chr_No (0-based: record chr{Chr_No + 1} of the genome), Start, End and one 0/1
+    column per name that begins with y_ (919 in the benchmark). ref_genome_version is hg19 or
+    hg38 and must be named by the coordinates file: the reference lifts hg19 coordinates over to
+    hg38 on the fly, which is not built here -- such a pair raises and says so.
+
+    The window of a row (FastaInterval.__call__): Start and End move outwards by
+    int((max_length - 1000) / 2) each; an interval shorter than max_length grows symmetrically
+    (the odd base to the right); what falls off either end of the chromosome becomes '.'; of an
+    interval longer than max_length the first max_length bases are kept. The window is
+    upper-cased and tokenised with the tokenizer's default call, so '.' is [UNK] and [SEP] is
+    appended: max_length + 1 ids for the benchmark's 1,000-base intervals. No padding, and no
+    reverse complement (the reference builds its interval reader without it).
+
+    Items are (ids int64, target fp32 [labels]) -- the dtype and shape DeepSEACsv gives, so head,
+    loss and AUROC are DeepSEA's. use_tokenizer=False (or id_remap=True): `remap_ids`.
+    genome: a genome.GenomeStore of the reference genome that the splits share; it is read from
+    ref_genome_path (.fa / .fna, plain or .gz) otherwise. `store` holds only the chromosomes
+    this split names; rows() gives every item's (src, n, left, right) for
+    resident.ResidentWindows."""
+
+    redraws = False
+
+    def __init__(self, data_path, ref_genome_path, ref_genome_version, split, max_length,
+                 tokenizer=None, use_tokenizer=True, id_remap=None, genome=None,
+                 coords_target_path=None):
+        from .genome import GenomeStore
+        self.max_length = int(max_length)
+        if self.max_length % 2:
+            raise ValueError(f"max_length {max_length}: the window must be even")
+        if ref_genome_version not in ("hg19", "hg38"):
+            raise ValueError('ref_genome_version must be "hg19" or "hg38"')
+        split = "val" if split in ("valid", "dev") else split
+        other = "hg38" if ref_genome_version == "hg19" else "hg19"
+        path = coords_target_path or os.path.join(
+            str(data_path), f"{split}_{ref_genome_version}_coords_targets.csv")
+        fn = os.path.basename(path)
+        if ref_genome_version not in fn or not os.path.exists(path):
+            alt = path if other in fn else os.path.join(
+                os.path.dirname(path), fn.replace(ref_genome_version, other))
+            if other in os.path.basename(alt) and os.path.exists(alt):
+                raise ValueError(
+                    f"{alt}: coordinates of {other}, but ref_genome_version={ref_genome_version!r}. "
+                    "Liftover between genome versions is not built here; convert the coordinates "
+                    f"first and name the file {split}_{ref_genome_version}_coords_targets.csv")
+            if not os.path.exists(path):
+                raise FileNotFoundError(
+                    f"{path}: no such file. The chromatin-profile tables are not downloaded here; "
+                    "put {train,val,test}_<version>_coords_targets.csv into <data_path>")
+            raise ValueError(f"{path}: the file name must carry the genome version "
+                             f"{ref_genome_version!r} of its coordinates")
+        self.path = path
+        self.tokenizer = tokenizer or CharacterTokenizer(["A", "C", "G", "T", "N"],
+                                                         self.max_length + 2)
+        self.id_remap = _want_remap(use_tokenizer, id_remap)
+        self.coords, rows = [], []
+        with open(path, newline="") as f:
+            reader = csv.reader(f)
+            header = next(reader, [])
+            missing = [c for c in ("Chr_No", "Start", "End") if c not in header]
+            if missing:
+                raise ValueError(f"{path}: no column {missing} in the header")
+            ci, si, ei = (header.index(c) for c in ("Chr_No", "Start", "End"))
+            self.target_columns = [c for c in header if c[:2] == "y_"]
+            ycols = [i for i, c in enumerate(header) if c[:2] == "y_"]
+            for row in reader:
+                if not row:
+                    continue
+                self.coords.append((int(row[ci]), int(row[si]), int(row[ei])))
+                rows.append(bytes(1 if row[i].strip() in ("1", "1.0", "True", "true") else 0
+                                  for i in ycols))
+        self.num_labels = self.d_output = len(ycols)
+        self.labels = (torch.frombuffer(bytearray(b"".join(rows)), dtype=torch.uint8)
+                       .reshape(len(rows), len(ycols)) if rows and ycols
+                       else torch.zeros(len(rows), len(ycols), dtype=torch.uint8))
+        if genome is None:
+            genome = GenomeStore.from_fasta(ref_genome_path)
+        names = sorted({f"chr{c + 1}" for c, _, _ in self.coords}, key=lambda s: int(s[3:]))
+        absent = [k for k in names if k not in genome]
+        if absent:
+            raise ValueError(f"{path}: names {absent}, which the reference genome does not hold")
+        self.store = genome.subset(names)
+        half = int((self.max_length - 1000) / 2)
+        self._windows = [self._window(f"chr{c + 1}", s - half, e + half)
+                         for c, s, e in self.coords]
+
+    def _window(self, name, start, end):
+        """FastaInterval.__call__ -> (record, first base, bases read, '.' before, '.' after)."""
+        length, ml = self.store.length(name), self.max_length
+        interval = end - start
+        if interval < ml:
+            extra = ml - interval
+            start -= extra // 2
+            end += extra - extra // 2
+        left = right = 0
+        if start < 0:
+            left, start = -start, 0
+        if end > length:
+            right, end = end - length, length
+        if interval > ml:
+            end = start + ml
+        cut = range(length)[start:end]  # what a Python slice of the record reads
+        return name, cut.start if len(cut) else 0, len(cut), left, right
+
+    def __len__(self):
+        return len(self.coords)
+
+    def __getitem__(self, idx):
+        name, start, n, left, right = self._windows[idx]
+        seq = "." * left + self.store.record(name)[start:start + n].decode("latin-1") + "." * right
+        ids = torch.tensor(self.tokenizer(seq.upper())["input_ids"], dtype=torch.int64)
+        if self.id_remap:
+            ids = remap_ids(ids)
+        return ids, self.labels[idx].to(torch.float32)
+
+    def rows(self):
+        """Every item's window -> (src int64 [N], n, left, right int32 [N])."""
+        src = torch.tensor([self.store.offset(w[0]) + w[1] for w in self._windows],
+                           dtype=torch.int64)
+        n, left, right = (torch.tensor([w[i] for w in self._windows], dtype=torch.int32)
+                          for i in (2, 3, 4))
+        return src, n, left, right
+
+    @property
+    def row_length(self):
+        return self.max_length + 1
+
+    def window_spec(self):
+        """(byte -> id table of the upper-cased byte, fill id = '.', eos id, tail id): [SEP]
+        follows the bases directly when no window runs off a chromosome's right end (eos id);
+        otherwise it is written into the last cell after the fill (tail id)."""
+        base = self.tokenizer._lut.astype("int64")
+        lut = torch.tensor([int(base[bytes([b]).upper()[0]]) for b in range(256)])
+        fill, sep = torch.tensor(int(base[ord(".")])), torch.tensor(self.tokenizer.sep_token_id)
+        if self.id_remap:
+            lut, fill, sep = remap_ids(lut), remap_ids(fill), remap_ids(sep)
+        runs_off = any(w[4] > 0 for w in self._windows)
+        return lut, int(fill), -1 if runs_off else int(sep), int(sep) if runs_off else -1
+
+    def collate(self, items):
+        return tuple(torch.stack(col) for col in zip(*items))

@@ -12,6 +12,11 @@ Randomness stays on the host, where the item-by-item path has it: the caller dra
 permutation, and the reverse-complement flags come from the dataset's own random.Random, one draw
 per item in access order, as `_CharItems._item` draws them. The same seeds give the same batches
 on both paths.
+
+ResidentWindows carries the same idea from per-sequence splits to whole genomes: the datasets
+that cut their windows out of chromosomes (species, chromatin_profile) keep a genome.GenomeStore
+on the device, and `dna_genome_windows` (csrc/genome_windows.hip) builds a batch from one
+(src, n, left) triple per row.
 """
 import numpy as np
 import torch
@@ -140,3 +145,110 @@ class ResidentSplit:
                self.eos_id, ids.data_ptr(), N.ptr(mask), N.stream_ptr(self.device))
         targets = self.targets.index_select(0, idx)
         return (ids, targets, mask) if self.return_mask else (ids, targets)
+
+
+class ResidentWindows:
+    """A split of finetune_data.SpeciesWindows or ChromatinProfile whose genome is on the device
+    (genome.GenomeStore.to): `batch(start, stop)` cuts rows [start, stop) of the current pass out
+    of it with `dna_genome_windows` (csrc/genome_windows.hip), integer-exact with
+    `collate([ds[j] ...])`. The interface is ResidentSplit's (__len__, set_epoch, batch).
+
+    Every decision stays on the host and only (src, n, left) per row goes up. A species split
+    draws a pass's windows at set_epoch -- three draws per entry of `order`, in order, from the
+    dataset's own random.Random, as that many accesses would (the entries themselves are ignored,
+    as the dataset ignores its index) -- so finetune.evaluate starts each pass with set_epoch, and
+    a train epoch followed by the val and test passes consumes a shared rng as item-by-item
+    access does. (A pass cut short, train.max_steps, has still drawn all its windows.) A
+    chromatin split's rows are fixed: they are computed and checked once here, and set_epoch
+    uploads the order alone."""
+
+    def __init__(self, ds, store):
+        """ds: the dataset (its rows / window_spec / row_length); store: ds.store.to(device)."""
+        self.ds, self.store, self.device = ds, store, store.device
+        if store.n_bases != ds.store.n_bases:
+            raise ValueError("ResidentWindows: the store is not the dataset's own")
+        self.n_bases, self.L = store.n_bases, int(ds.row_length)
+        lut, self.fill_id, self.eos_id, self.tail_id = ds.window_spec()
+        if lut.shape != (256,) or int(lut.min()) < 0 or self.fill_id < 0:
+            raise ValueError("ResidentWindows: the id table is int64 [256], non-negative")
+        self.lut = lut.to(self.device)
+        self.redraws = bool(ds.redraws)
+        if not self.redraws:
+            src, n, left, right = ds.rows()
+            if bool((left + n + right != self.L - 1).any()):
+                bad = int((left + n + right != self.L - 1).nonzero()[0])
+                raise ValueError(f"ResidentWindows: item {bad} is {int((left + n + right)[bad])} "
+                                 f"characters long, not {self.L - 1}; a resident split builds "
+                                 "rectangles only (intervals of one length)")
+            self._check(src, n, left)
+            self._all = tuple(t.to(self.device) for t in (src, n, left))
+            self.targets = ds.labels.to(self.device)
+        self._rows = self._targets = self._order = None
+        self._count = len(ds)
+        if not self.redraws:
+            self.set_epoch()
+
+    @classmethod
+    def from_dataset(cls, ds, device):
+        return cls(ds, ds.store.to(device))
+
+    def _check(self, src, n, left):
+        """What the kernel would write as fill is an error here, before anything is uploaded."""
+        if src.numel() and (int(src.min()) < 0 or int(n.min()) < 0 or int(left.min()) < 0
+                            or int((src + n).max()) > self.n_bases):
+            raise ValueError("ResidentWindows: a window lies outside the genome store")
+
+    def __len__(self):
+        return len(self.ds)
+
+    def device_bytes(self):
+        """Bytes this split holds on the device between batches."""
+        held = [self.store.bases, self.lut] + list(self._rows or ()) + \
+            ([] if self.redraws else list(self._all) + [self.targets]) + \
+            ([self._targets] if self._targets is not None else [])
+        return sum(t.numel() * t.element_size() for t in held)
+
+    def set_epoch(self, order=None):
+        """Starts a pass of len(order) rows (None: one per item, in the dataset's order)."""
+        if self.redraws:
+            k = len(self.ds) if order is None else len(order)
+            src, n, left, tgt = self.ds.rows(k)
+            self._check(src, n, left)
+            self._rows = tuple(t.to(self.device) for t in (src, n, left))
+            self._targets, self._order, self._count = tgt.to(self.device), None, k
+            return
+        if order is None:
+            self._rows, self._order, self._count = self._all, None, len(self.ds)
+            return
+        order = torch.as_tensor(list(order) if isinstance(order, range) else order,
+                                dtype=torch.int64).reshape(-1)
+        if order.numel() and (int(order.min()) < 0 or int(order.max()) >= len(self.ds)):
+            raise IndexError(f"ResidentWindows.set_epoch: order has entries outside "
+                             f"[0, {len(self.ds)})")
+        self._order = order.to(self.device)
+        self._rows = tuple(t.index_select(0, self._order) for t in self._all)
+        self._count = int(order.numel())
+
+    def batch(self, start, stop):
+        """Rows [start, stop) of the pass -> (ids int64 [b, row_length], targets) on the device."""
+        if self._rows is None:
+            raise RuntimeError("ResidentWindows.batch before set_epoch: no windows are drawn yet")
+        start, stop = max(0, int(start)), min(int(stop), self._count)
+        if stop <= start:
+            raise IndexError(f"ResidentWindows.batch: empty range [{start}, {stop})")
+        src, n, left = (t[start:stop] for t in self._rows)
+        b = stop - start
+        ids = torch.empty((b, self.L), dtype=torch.int64, device=self.device)
+        N.call("dna_genome_windows", self.store.bases.data_ptr(), self.n_bases, src.data_ptr(),
+               n.data_ptr(), left.data_ptr(), self.lut.data_ptr(), b, self.L, self.fill_id,
+               self.eos_id, ids.data_ptr(), N.stream_ptr(self.device))
+        if self.tail_id >= 0:  # a window runs off a right end: [SEP] stands after the fill
+            ids[:, self.L - 1] = self.tail_id
+        if self.redraws:
+            return ids, self._targets[start:stop]
+        idx = (self._order[start:stop] if self._order is not None
+               else torch.arange(start, stop, device=self.device))
+        return ids, self.targets.index_select(0, idx).to(torch.float32)
+
+
+RESIDENT = (ResidentSplit, ResidentWindows)

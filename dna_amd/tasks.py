@@ -72,10 +72,19 @@ class ConfusionMatrix:
     pooled predictions of the epoch (what the GUE tables report; equal to
     sklearn.metrics.matthews_corrcoef / f1_score(average="macro") on them). The reference calls
     sklearn per batch instead and averages the per-batch values (src/tasks/metrics.py:83-87,
-    :229-233)."""
+    :229-233).
 
-    def __init__(self, num_classes):
+    per_class: which of PER_CLASS compute() adds -- lists in class order, a class that never
+    occurs (as a label for accuracy / recall, as a prediction for precision) reported as 0. The
+    reference's species experiment names them in task.metrics and defines none of them; here
+    accuracy_per_class is the fraction of a class's sequences that are classified as it, which
+    for one label per sequence is its recall."""
+
+    PER_CLASS = ("accuracy_per_class", "precision_per_class", "recall_per_class")
+
+    def __init__(self, num_classes, per_class=()):
         self.num_classes = int(num_classes)
+        self.per_class = tuple(m for m in self.PER_CLASS if m in tuple(per_class))
         self.reset()
 
     def reset(self):
@@ -109,7 +118,11 @@ class ConfusionMatrix:
         present = (t + p) > 0
         f1 = torch.where(tp > 0, 2 * tp / (t + p).clamp(min=1), torch.zeros_like(tp))
         f1_macro = f1[present].mean().item() if present.any() else 0.0
-        return {"accuracy": acc, "mcc": mcc, "f1_macro": f1_macro}
+        out = {"accuracy": acc, "mcc": mcc, "f1_macro": f1_macro}
+        ratio = lambda den: torch.where(den > 0, tp / den.clamp(min=1), torch.zeros_like(tp)).tolist()
+        for name in self.per_class:
+            out[name] = ratio(p if name == "precision_per_class" else t)
+        return out
 
 
 class PearsonR:

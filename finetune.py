@@ -39,6 +39,15 @@ task table (finetune_data.NT_TASKS) unless given, with the cosine_warmup_timm sc
 
     python finetune.py experiment=hyena/nt_hyena dataset.dest_path=/data/nt dataset.dataset_name=H3
 
+dataset._name_ species (a random window of a random chromosome of a random species, classified
+by species; dataset.species_dir holds <species>/chr<name>.fna) and chromatin_profile (919
+chromatin features of a window centred on a coordinate of hg19 / hg38; dataset.data_path holds the
+coordinates tables, dataset.ref_genome_path the genome) cut their windows out of whole genomes:
+
+    python finetune.py experiment=hyena/species_hyena dataset.species_dir=/data/species
+    python finetune.py experiment=hyena/chromatin_profile_hyena dataset.data_path=/data/chromatin \\
+        dataset.ref_genome_path=/data/hg38/hg38.ml.fa
+
 dataset.resident=true (the pooling models; every dataset above) keeps the splits on the device and
 builds each batch there with one HIP kernel (dna_amd.resident), bit-identical to the item-by-item
 path for the same seeds.
@@ -130,29 +139,33 @@ def _nt_defaults(cfg):
         cfg.train["mode"] = "max"
 
 
-def _metric(problem_type, num_labels):
+def _metric(problem_type, num_labels, per_class=()):
     """The evaluator of a problem type: (accumulator, whether it reads the logits -- or the
-    head's argmax). Single-label: accuracy, mcc, f1_macro; regression: pearsonr_dev, pearsonr_hk
-    (the DeepSTARR targets' names) and pearsonr_mean; multi-label: roc, roc_labels_skipped."""
+    head's argmax). Single-label: accuracy, mcc, f1_macro (+ the *_per_class lists that
+    task.metrics names); regression: pearsonr_dev, pearsonr_hk (the DeepSTARR targets' names)
+    and pearsonr_mean; multi-label: roc, roc_labels_skipped."""
     from dna_amd.tasks import ConfusionMatrix, MultilabelAUROC, PearsonR
     if problem_type == "regression":
         names = ("dev", "hk") if num_labels == 2 else tuple(str(i) for i in range(num_labels))
         return PearsonR(names), True
     if problem_type == "multi_label_classification":
         return MultilabelAUROC(num_labels), True
-    return ConfusionMatrix(num_labels), False
+    return ConfusionMatrix(num_labels, per_class), False
 
 
 @torch.no_grad()
 def evaluate(trainer, ds, batch_size, device, num_labels,
-             problem_type="single_label_classification", unpad=False):
+             problem_type="single_label_classification", unpad=False, per_class=()):
     """-> {"loss", ...the problem type's metrics (_metric)} of one split; the metric's state
     stays on the device until the split is done. unpad: packed batches (dataset.unpad). A
-    resident.ResidentSplit builds its batches on the device, in the split's own order."""
-    from dna_amd.resident import ResidentSplit
-    metric, on_logits = _metric(problem_type, num_labels)
+    resident.ResidentSplit builds its batches on the device, in the split's own order; a
+    resident.ResidentWindows starts a pass of its own (a species split draws its windows then)."""
+    from dna_amd.resident import RESIDENT, ResidentWindows
+    metric, on_logits = _metric(problem_type, num_labels, per_class)
     total = torch.zeros((), device=device, dtype=torch.float64)
-    resident = isinstance(ds, ResidentSplit)
+    resident = isinstance(ds, RESIDENT)
+    if isinstance(ds, ResidentWindows):
+        ds.set_epoch()
     for i in range(0, len(ds), batch_size):
         if resident:
             (ids, labels), packed = ds.batch(i, i + batch_size)[:2], None
@@ -265,13 +278,45 @@ def load_pretrained(model, state_dict, freeze_backbone=False):
     return {"missing": list(missing), "unexpected": len(unexpected)}
 
 
-POOL_DATASETS = ("genomic_benchmark", "deepstarr", "deepsea", "nucleotide_transformer")
+POOL_DATASETS = ("genomic_benchmark", "deepstarr", "deepsea", "nucleotide_transformer",
+                 "species", "chromatin_profile")
+GENOME_DATASETS = ("species", "chromatin_profile")  # windows cut out of whole genomes
 
 
-def _pool_splits(ds, tok, max_length):
+def _genome_defaults(cfg):
+    """dataset._name_ species: d_output is the number of species, and a null train_len (the
+    cosine schedule's length) is the train split's size, total_size * ((max_length_test + 2) //
+    max_length). chromatin_profile: a null d_output is the number of y_* columns of the train
+    table when dataset.data_path is there to read, DeepSEA's 919 otherwise. Idempotent."""
+    ds = cfg.get("dataset")
+    if ds is None or ds.get("_name_") not in GENOME_DATASETS:
+        return
+    from dna_amd import finetune_data as FD
+    if ds._name_ == "species":
+        if ds.get("task", "species_classification") == "next_token_pred":
+            raise NotImplementedError("dataset.task=next_token_pred is not built; "
+                                      "species_classification only")
+        ds["d_output"] = len(ds.species)
+        if ds.get("train_len") is None:
+            ds["train_len"] = FD.species_split_sizes(
+                ds.total_size, int(ds.max_length), ds.get("max_length_val"),
+                ds.get("max_length_test"))["train"][0]
+    elif ds.get("d_output") is None:
+        path = os.path.join(str(ds.get("data_path")),
+                            f"train_{ds.get('ref_genome_version')}_coords_targets.csv")
+        if ds.get("data_path") and os.path.exists(path):
+            with open(path) as f:
+                ds["d_output"] = sum(c.strip()[:2] == "y_" for c in f.readline().split(","))
+        else:
+            ds["d_output"] = FD.DEEPSEA_LABELS
+
+
+def _pool_splits(ds, tok, max_length, seed=None):
     """dataset._name_ -> {"train", "dev", "test": dataset}. Genomic Benchmarks have no validation
     split (dev is the test folder); DeepSTARR and DeepSEA have their own train / val / test
-    files; the Nucleotide Transformer benchmark has no validation split either."""
+    files; the Nucleotide Transformer benchmark has no validation split either. species and
+    chromatin_profile cut windows out of genomes; seed: of the generator the species splits draw
+    their windows from."""
     from dna_amd import finetune_data as FD
     # dataset.use_tokenizer=false (the one-hot models): ids A C G T N = 0..4 (finetune_data.remap_ids)
     kw = dict(max_length=max_length, tokenizer=tok, use_padding=ds.get("use_padding", True),
@@ -288,6 +333,30 @@ def _pool_splits(ds, tok, max_length):
             ds.dest_path, ds.dataset_name, split, d_output=ds.get("d_output"), **kw, **k)
         test_ds = make("val")
         return {"train": make("train", rc_aug=rc), "dev": test_ds, "test": test_ds}
+    if name == "species":
+        import random
+        # one generator for the three splits, as the reference's share the global one
+        rng = random.Random(seed)
+        sizes = FD.species_split_sizes(ds.total_size, max_length, ds.get("max_length_val"),
+                                       ds.get("max_length_test"))
+        weights = lambda w: w.to_container() if hasattr(w, "to_container") else w
+        make = lambda split: FD.SpeciesWindows(
+            list(ds.species), ds.species_dir, split, sizes[split][1], sizes[split][0],
+            tokenizer=tok, add_eos=ds.get("add_eos", True), rng=rng,
+            species_weights=weights(ds.get("species_weights", "uniform")),
+            chromosome_weights=weights(ds.get("chromosome_weights", "uniform")),
+            task=ds.get("task", "species_classification"),
+            remove_tail_ends=ds.get("remove_tail_ends", False),
+            cutoff_train=ds.get("cutoff_train", 0.1), cutoff_test=ds.get("cutoff_test", 0.2),
+            id_remap=kw["id_remap"])
+        return {"train": make("train"), "dev": make("valid"), "test": make("test")}
+    if name == "chromatin_profile":
+        from dna_amd.genome import GenomeStore
+        genome = GenomeStore.from_fasta(ds.ref_genome_path)  # read once, shared by the splits
+        make = lambda split: FD.ChromatinProfile(
+            ds.data_path, ds.ref_genome_path, ds.ref_genome_version, split, max_length,
+            tokenizer=tok, id_remap=kw["id_remap"], genome=genome)
+        return {"train": make("train"), "dev": make("val"), "test": make("test")}
     if name == "deepstarr":
         make = lambda split, **k: FD.DeepSTARRFolder(ds.dest_path, split, **kw, **k)
     else:
@@ -311,9 +380,11 @@ def finetune_pool(cfg, dry_run=False, out=sys.stdout):
     if ds.get("_name_", "genomic_benchmark") not in POOL_DATASETS:
         raise ValueError(f"dataset._name_={ds.get('_name_')!r}: one of {POOL_DATASETS}")
     _nt_defaults(cfg)
+    _genome_defaults(cfg)
     sched = _scheduler(cfg)
     opt = cfg.optimizer.to_container()
     resident = bool(ds.get("resident", False))
+    genome = ds.get("_name_") in GENOME_DATASETS
     if resident and not ds.get("use_padding", True):
         raise ValueError("dataset.resident=true with dataset.use_padding=false: ragged items have "
                          "no fixed length, a resident split builds rectangles only")
@@ -330,15 +401,23 @@ def finetune_pool(cfg, dry_run=False, out=sys.stdout):
                           "loss_scale": model.loss_scale, "dataset": ds.get("_name_"),
                           "dest_path": ds.get("dest_path"),
                           "dataset_name": ds.get("dataset_name"), "max_length": max_length,
+                          "d_output": ds.get("d_output"),
                           "resident": resident, "scheduler_name": _scheduler_name(cfg),
                           "monitor": cfg.train.monitor, "mode": cfg.train.mode,
                           "scheduler": sched, "optimizer": opt}), file=out)
         return None
-    if not ds.get("dest_path"):
+    if ds.get("_name_") == "species" and not ds.get("species_dir"):
+        raise ValueError("dataset.species_dir=<folder of <species>/chr*.fna> is required")
+    if ds.get("_name_") == "chromatin_profile" and not (ds.get("data_path")
+                                                        and ds.get("ref_genome_path")):
+        raise ValueError("dataset.data_path=<folder of the coordinates tables> and "
+                         "dataset.ref_genome_path=<the genome's FASTA> are required")
+    if not genome and not ds.get("dest_path"):
         raise ValueError("dataset.dest_path=<folder holding the dataset's files> is required "
                          "(genomic_benchmark: <dataset_name>/train and /test)")
-    splits = _pool_splits(ds, tok, max_length)
-    num_labels = int(ds.get("d_output") or splits["train"].num_labels)
+    splits = _pool_splits(ds, tok, max_length, seed=seed)
+    num_labels = int(splits["train"].num_labels if genome
+                     else ds.get("d_output") or splits["train"].num_labels)
     model = _pool_model(cfg, num_labels, tok)
     pre = cfg.train.get("pretrained_model_path")
     if pre:
@@ -361,11 +440,12 @@ def finetune_pool(cfg, dry_run=False, out=sys.stdout):
     if resident:
         # each split once (dev and test may be one dataset): bytes, offsets and targets go to the
         # device here, and _fit / evaluate take their batches from there
-        from dna_amd.resident import ResidentSplit
+        from dna_amd.resident import ResidentSplit, ResidentWindows
+        cls = ResidentWindows if genome else ResidentSplit
         made = {}
         for name, split in list(splits.items()):
             if id(split) not in made:
-                made[id(split)] = ResidentSplit.from_dataset(split, device)
+                made[id(split)] = cls.from_dataset(split, device)
             splits[name] = made[id(split)]
     return _fit(cfg, trainer, model, splits, device, out)
 
@@ -451,8 +531,11 @@ def _fit(cfg, trainer, model, splits, device, out):
     log_every = int(cfg.trainer.get("log_every_n_steps", 10))
     max_steps = cfg.train.get("max_steps")
     unpad = bool(cfg.dataset.get("unpad", False))  # packed batches: no kernel runs on [PAD] rows
-    from dna_amd.resident import ResidentSplit
-    resident = isinstance(train_ds, ResidentSplit)
+    from dna_amd.resident import RESIDENT
+    resident = isinstance(train_ds, RESIDENT)
+    # the *_per_class lists are reported only where task.metrics asks for them
+    per_class = [m for m in ((cfg.get("task") or {}).get("metrics") or [])
+                 if str(m).endswith("_per_class")]
     gen = torch.Generator().manual_seed(int(cfg.train.get("seed") or 0))
     print(json.dumps({"event": "start", "train": len(train_ds), "dev": len(splits["dev"]),
                       "test": len(splits["test"]), "num_labels": model.num_labels,
@@ -488,7 +571,8 @@ def _fit(cfg, trainer, model, splits, device, out):
         for name, split in (("val", "dev"), ("test", "test")):
             for k, v in evaluate(trainer, splits[split], ebs, device, model.num_labels,
                                  getattr(model, "problem_type", None)
-                                 or "single_label_classification", unpad=unpad).items():
+                                 or "single_label_classification", unpad=unpad,
+                                 per_class=per_class).items():
                 metrics[f"{name}/{k}"] = v
         print(json.dumps(dict({"event": "eval", "epoch": epoch, "step": trainer.global_step},
                               **metrics)), file=out, flush=True)
@@ -518,6 +602,7 @@ def main(argv=None):
         overrides.insert(0, "experiment=" + EXPERIMENT)
     cfg = compose(a.config_dir, a.config_name, overrides)
     _nt_defaults(cfg)
+    _genome_defaults(cfg)
     if a.print_config or a.dry_run:
         print(json.dumps(cfg.to_container(skip_errors=True), indent=1, default=str))
     return finetune(cfg, dry_run=a.dry_run)

@@ -26,8 +26,8 @@ extern "C" {
 /* Counts additions that leave every version-1 entry point as it was (a caller built against an
  * earlier revision keeps working): 1 = dna_lm_head_*, 2 = dna_lm_head_rc_*, 3 = dna_attn_varlen_*,
  * 4 = dna_dconv_* / dna_onehot_conv_*, 5 = dna_selective_scan_plan, 6 = dna_lm_head_bias_* and
- * DNA_ACT_RELU in dna_onehot_conv_*, 7 = dna_char_batch. */
-#define DNA_AMD_ABI_REVISION 7
+ * DNA_ACT_RELU in dna_onehot_conv_*, 7 = dna_char_batch, 8 = dna_genome_windows. */
+#define DNA_AMD_ABI_REVISION 8
 
 enum dna_status {
   DNA_OK = 0,
@@ -855,6 +855,17 @@ int dna_char_batch(const uint8_t* bases, int64_t n_bases, const int64_t* offsets
                    const int64_t* idx, const uint8_t* rc, const int64_t* lut, const uint8_t* comp,
                    int B, int L, int pad_left, int64_t pad_id, int64_t eos_id, int64_t* ids,
                    uint8_t* mask, void* stream);
+
+/* One batch of character tokens cut out of a device-resident genome (csrc/genome_windows.hip):
+ * `bases` holds the records of a genome store, one byte per base, concatenated (n_bases may
+ * exceed 2^31). Row r of ids int64 [B, L] is, cut at L cells: fill_id on left[r] cells, then
+ * lut[bases[src[r] + j]] for j < n[r], then eos_id when it is >= 0, then fill_id. src int64 [B]
+ * (absolute offsets), n and left int32 [B], lut int64 [256], all on the device. Every cell is
+ * written exactly once. A row with src < 0, n < 0, left < 0 or src + n > n_bases is written as
+ * all fill_id; nothing outside bases[src .. src + n) is read. */
+int dna_genome_windows(const uint8_t* bases, int64_t n_bases, const int64_t* src, const int32_t* n,
+                       const int32_t* left, const int64_t* lut, int B, int L, int64_t fill_id,
+                       int64_t eos_id, int64_t* ids, void* stream);
 
 /* ------------------------------------------------------------------ data path (host, C++)
  * BPE tokenizer: bit-exact with the reference's HF `tokenizers` BPE for
