@@ -25,7 +25,17 @@
 // Block order: bijective XCD remap (blocks sharing an L2 get consecutive tile ids), then
 // groups of GM row-tiles swept column-fastest so a group's A panels stay L2-resident while the
 // weight (<= 9.4 MB, MALL-resident) streams.
+// Kernels (every instantiation is one the default dispatch reaches; see the launchers at the end):
+//   gemm_kernel<AK, BKM, EPI>   one tile per block: dgrad / wgrad on [K][N] operands, and the
+//                               forward shapes the persistent kernel does not take
+//   gemmp_kernel<EPI, SCH>      persistent, both operands K-major; SCH 2 = the lean K-step body
+//                               (even K / 64), SCH 0 = the older body for any step count
+//                               (EPI_BF16 and EPI_GEGLU only)
+//   wgradp_kernel<SCH>          persistent token-major weight gradient; SCH 2 in K-step pairs,
+//                               SCH 0 where whole pairs would push a chunk past 2^31 bytes
 #include <stdlib.h>
+
+#include <string>
 
 #include <type_traits>
 
@@ -159,10 +169,12 @@ struct Args {
   int tilesM, tilesN, GM;
   int F;
   float p; uint32_t th; float ks; uint64_t seed, off;
+  // The four fields below are always 0: no launcher sets them and no switch reads them any more.
+  // They and the branches they guard stay in gemmp_kernel because taking them out made the bf16
+  // forward 0.3-0.6 % slower per launch (DESIGN, "GEMM variants removed").
   int rot;                    // persistent kernel: rotate each block's K order (store spreading)
-  int dbg;                    // diagnostics (DNA_GEMM_DBG): 1 = stores dropped (OOB), 2 = no stores,
-                              // 4 = output stores with the sc0 cache policy (A/B)
-  int nt;                     // persistent kernel: non-temporal output stores (DNA_GEMM_NT, default 0)
+  int dbg;                    // 1 = stores dropped (OOB), 2 = no stores, 4 = stores with the sc0 policy
+  int nt;                     // persistent kernel: non-temporal output stores
   int order;                  // persistent kernel unit order: 0 = round-robin over the grid (XCD-
                               // remapped), 1 = XCD-major (each XCD sweeps one contiguous unit range)
 };
@@ -552,42 +564,15 @@ __device__ __forceinline__ void unit_tile(const Args& a, int u, int& m0, int& n0
   n0 = (w / gsz) * (EPI == EPI_GEGLU ? BN / 2 : BN);
 }
 
-// ABL (diagnostic ablations of the main loop, DNA_GEMM_ABL; results are garbage, timing only):
-// 1 = no LDS-DMA staging, 2 = no LDS reads (MFMAs on stale fragments), 4 = no barriers,
-// 8 = no B staging and no B reads, 16 = no B reads, 32 = no B staging
-// SCH == 1 schedules: 16-B stores (per lane) issued after the stage of phase P-5 and before the
-// wait of phase P, for a K-step of role r (see gemmp_kernel) and phase p. The previous unit's
-// last K-step is phases -4..-1, the current unit's starts at lb. EPI_F32 = the weight-gradient
-// kernel (8 fp32 stores per quadrant), EPI_BF16 4 per quadrant, EPI_GEGLU 12 after phases 1, 3.
-template <int EPI>
-__host__ __device__ constexpr int pend_stores(int r, int p) {
-  const int P = r == 1 ? p : r == 3 ? 400 + p : 4 + p;
-  const int lb = r == 3 ? 400 : r == 4 ? 4 : 1 << 20;
-  int n = 0;
-  for (int q = 0; q < 4; ++q) {
-    const int st = EPI == EPI_F32 ? 8 : EPI == EPI_BF16 ? 4 : ((q & 1) ? 12 : 0);
-    const int sp = q - 4, sc = lb + q;
-    if (sp >= P - 5 && sp <= P - 1) n += st;
-    if (sc >= P - 5 && sc <= P - 1) n += st;
-  }
-  return n;
-}
-static_assert(pend_stores<EPI_BF16>(1, 0) == 16 && pend_stores<EPI_BF16>(1, 3) == 8 &&
-              pend_stores<EPI_BF16>(2, 0) == 4 && pend_stores<EPI_BF16>(2, 1) == 0 &&
-              pend_stores<EPI_BF16>(3, 0) == 0 && pend_stores<EPI_BF16>(3, 3) == 12 &&
-              pend_stores<EPI_BF16>(4, 0) == 4 && pend_stores<EPI_BF16>(4, 1) == 4 &&
-              pend_stores<EPI_GEGLU>(1, 3) == 12 && pend_stores<EPI_GEGLU>(4, 2) == 12,
-              "SCH 1 store counts");
-
-// SCH selects the half-tile schedule: 0 = the original 4-phase order (reads 12/4/8/0 per phase),
-// 1 = balanced reads (8/4/8/4: B_0 of the next K-step is read in phase 3) with 5 half-tiles in
-// flight -- see the comment above the SCH == 1 branch
-template <int EPI, int ABL = 0, int SCH = 0>
+// SCH selects the K-step body of the 4-phase schedule: 0 = one role-branching copy for any K-step
+// count, 2 = the lean body (K-steps unrolled by two: an even count only) -- see the SCH == 2 branch
+template <int EPI, int SCH>
 __global__ __launch_bounds__(NTHR) void gemmp_kernel(Args a) {
+  static_assert(SCH == 0 || SCH == 2, "persistent kernel: bodies SCH 0 and SCH 2");
   static_assert(EPI == EPI_BF16 || EPI == EPI_GEGLU ||
-                    (EPI == EPI_GEGLU_BWD && SCH == 2 && (ABL == 0 || ABL == 128)) ||
-                    ((EPI == EPI_GELU_BWD || EPI == EPI_BF16_GELU) && SCH == 2 && ABL == 0),
-                "persistent kernel: bf16 / GeGLU epilogues (GeGLU backward: lean body only)");
+                    ((EPI == EPI_GEGLU_BWD || EPI == EPI_GELU_BWD || EPI == EPI_BF16_GELU) && SCH == 2),
+                "persistent kernel: bf16 / GeGLU forward epilogues take both bodies, the GeGLU / "
+                "GELU backward and bf16 + GELU epilogues the lean body only");
   __shared__ __attribute__((aligned(1024))) char smem[LDS_BYTES + BIAS_LDS];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -613,7 +598,6 @@ __global__ __launch_bounds__(NTHR) void gemmp_kernel(Args a) {
   if (nb == 0) return;
   const int L = ubase;
   const int KT = a.K / BK;
-  const int V = nb * KT;
   float* bias_lds = reinterpret_cast<float*>(smem + LDS_BYTES);
   const int nbias = EPI == EPI_GEGLU ? 2 * a.F : (EPI == EPI_GEGLU_BWD || EPI == EPI_GELU_BWD) ? 0 : a.N;
   for (int c = tid * 4; c < nbias; c += NTHR * 4)
@@ -743,8 +727,8 @@ __global__ __launch_bounds__(NTHR) void gemmp_kernel(Args a) {
       // row block in voffset (range-checked: rows past M are dropped), never in soffset
       const uint32_t off = voQ + (uint32_t)__builtin_amdgcn_readfirstlane(
                                      ((c.m0 + mq * 128 + i * 16) * a.ldc + c.n0 + nq * 128) * 2);
-      // DNA_GEMM_NT=1 streams the output tiles with the non-temporal policy (aux 2): +2-9 % on
-      // isolated K = 768 GEMMs, but -1 % on the training step (the next kernel reads them), so off
+      // a.nt (always 0) would stream the output tiles with the non-temporal policy (aux 2): +2-9 %
+      // on isolated K = 768 GEMMs, but -1 % on the training step (the next kernel reads them)
       if (a.dbg == 0) {
         if (a.nt) __builtin_amdgcn_raw_buffer_store_b128(o, rC, off, 0, 2);
         else __builtin_amdgcn_raw_buffer_store_b128(o, rC, off, 0, 0);
@@ -848,58 +832,48 @@ __global__ __launch_bounds__(NTHR) void gemmp_kernel(Args a) {
   using P2 = std::integral_constant<int, 2>;
   using P3 = std::integral_constant<int, 3>;
   auto kstep = [&](int v, int role) {
-    auto stg = [&](const Cur& c, int vv, int h) {
-      if constexpr (!(ABL & 1)) {
-        if (!(ABL & 40) || h < 2) stage(c, vv, h);
-      }
-    };
-    auto rdA = [&](int vv, int mq) { if constexpr (!(ABL & 2)) readA(vv, mq); };
-    auto rdB = [&](int vv, int nq, bf16x8 (&bf)[2][2]) {
-      if constexpr (!(ABL & 2) && !(ABL & 24)) readB(vv, nq, bf);
-    };
-    auto bar = [&]() { if constexpr (!(ABL & 4)) { DNA_BARRIER(); } else { __builtin_amdgcn_sched_barrier(0); } };
     const bool st = EPI == EPI_BF16 && role == 1;
     const bool sg = EPI == EPI_GEGLU && role == 1;
     // phase 0: quadrant (0,0)
-    stg(c1, v + 1, 3);
+    stage(c1, v + 1, 3);
     wait_vm(P0{}, role);
-    rdA(v, 0);
-    rdB(v, 0, bf0);
-    bar();
+    readA(v, 0);
+    readB(v, 0, bf0);
+    DNA_BARRIER();
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_sched_barrier(0);
     mma(0, 0, bf0);
     if (st) store_quadrant(c0, 0, 0);
-    bar();
+    DNA_BARRIER();
     // phase 1: quadrant (0,1)
-    stg(c1, v + 1, 1);
+    stage(c1, v + 1, 1);
     wait_vm(P1{}, role);
-    rdB(v, 1, bf1);
-    bar();
+    readB(v, 1, bf1);
+    DNA_BARRIER();
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_sched_barrier(0);
     mma(0, 1, bf1);
     if (st) store_quadrant(c0, 0, 1);
     if (sg) store_geglu_half(c0, 0);
-    bar();
+    DNA_BARRIER();
     // phase 2: quadrant (1,1)
-    stg(c2, v + 2, 0);
+    stage(c2, v + 2, 0);
     wait_vm(P2{}, role);
-    rdA(v, 1);
-    bar();
+    readA(v, 1);
+    DNA_BARRIER();
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_sched_barrier(0);
     mma(1, 1, bf1);
     if (st) store_quadrant(c0, 1, 1);
-    bar();
+    DNA_BARRIER();
     // phase 3: quadrant (1,0)
-    stg(c2, v + 2, 2);
+    stage(c2, v + 2, 2);
     wait_vm(P3{}, role);
-    bar();
+    DNA_BARRIER();
     mma(1, 0, bf0);
     if (st) store_quadrant(c0, 1, 0);
     if (sg) store_geglu_half(c0, 1);
-    bar();
+    DNA_BARRIER();
   };
 
   int v = 0;
@@ -912,115 +886,6 @@ __global__ __launch_bounds__(NTHR) void gemmp_kernel(Args a) {
     }
     c0 = cur_at(i + 1);
   }
-  } else if constexpr (SCH == 1) {
-    // SCH == 1. Per K-step v (quadrant order (0,0) (0,1) (1,1) (1,0)):
-    //   phase  reads        stages         MFMAs with
-    //   0      A_0(v)       S(v+1, A_1)    A_0, B_0(v) (read in phase 3 of step v-1)
-    //   1      B_1(v)       S(v+2, B_0)    A_0, B_1
-    //   2      A_1(v)       S(v+2, A_0)    A_1, B_1
-    //   3      B_0(v+1)     S(v+2, B_1)    A_1, B_0(v)
-    // Every phase reads at most 8 fragments per wave (the SCH 0 order reads 12 in phase 0, whose
-    // LDS time plus the DMA writes then outlasts the partner wave's 16-MFMA cluster). The two B
-    // register sets swap roles every K-step. WAR: every half is restaged 2 phases after its last
-    // read (the other wave group's reads of the phase before may still be in flight). RAW: a
-    // half read in phase P was staged in phase P-6 or earlier and is retired by the wait of phase
-    // P-1 (then a barrier), which leaves the 5 youngest half-tiles (10 LDS-DMA pieces per lane) in
-    // flight plus every epilogue store issued after the retiring stage -- the stores of a unit's
-    // last K-step sit in the same in-order VMEM count.
-    constexpr int hA0 = 0, hA1 = 1, hB0 = 2, hB1 = 3;
-    // step roles: 0 = no store pending in any wait window, 1 = a unit's first K-step after an
-    // epilogue, 2 = its second, 3 = a unit's last K-step (KT > 2, or the block's first unit),
-    // 4 = second and last at once (KT == 2 after an epilogue). pend_stores<EPI>(role, p) is the
-    // number of 16-B stores issued after the stage of phase P-5 and before the wait of phase P.
-    auto wait_p = [&](auto phase, int role) {
-      constexpr int p = decltype(phase)::value;
-      if (role == 0) __builtin_amdgcn_s_waitcnt(waitcnt_imm(10));
-      else if (role == 1) __builtin_amdgcn_s_waitcnt(waitcnt_imm(10 + pend_stores<EPI>(1, p)));
-      else if (role == 2) __builtin_amdgcn_s_waitcnt(waitcnt_imm(10 + pend_stores<EPI>(2, p)));
-      else if (role == 3) __builtin_amdgcn_s_waitcnt(waitcnt_imm(10 + pend_stores<EPI>(3, p)));
-      else __builtin_amdgcn_s_waitcnt(waitcnt_imm(10 + pend_stores<EPI>(4, p)));
-    };
-    auto lgkm0 = [&]() {
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      __builtin_amdgcn_sched_barrier(0);
-    };
-    auto step = [&](int v, int kt, bool prev, bf16x8 (&bB0)[2][2], bf16x8 (&bB1)[2][2]) {
-      const bool last = kt == KT - 1;
-      const int role = __builtin_amdgcn_readfirstlane(
-          last ? (prev && kt == 1 ? 4 : 3) : prev && kt == 0 ? 1 : prev && kt == 1 ? 2 : 0);
-      const bool st = EPI == EPI_BF16 && last;
-      const bool sg = EPI == EPI_GEGLU && last;
-      // phase 0: quadrant (0,0)
-      stage(c1, v + 1, hA1);
-      wait_p(std::integral_constant<int, 0>{}, role);
-      readA(v, 0);
-      DNA_BARRIER();
-      lgkm0();
-      mma(0, 0, bB0);
-      if (st) store_quadrant(c0, 0, 0);
-      DNA_BARRIER();
-      // phase 1: quadrant (0,1)
-      stage(c2, v + 2, hB0);
-      wait_p(std::integral_constant<int, 1>{}, role);
-      readB(v, 1, bB1);
-      DNA_BARRIER();
-      lgkm0();
-      mma(0, 1, bB1);
-      if (st) store_quadrant(c0, 0, 1);
-      if (sg) store_geglu_half(c0, 0);
-      DNA_BARRIER();
-      // phase 2: quadrant (1,1)
-      stage(c2, v + 2, hA0);
-      wait_p(std::integral_constant<int, 2>{}, role);
-      readA(v, 1);
-      DNA_BARRIER();
-      lgkm0();
-      mma(1, 1, bB1);
-      if (st) store_quadrant(c0, 1, 1);
-      DNA_BARRIER();
-      // phase 3: quadrant (1,0); B_0 of the next K-step into the set B_1 just left
-      stage(c2, v + 2, hB1);
-      wait_p(std::integral_constant<int, 3>{}, role);
-      readB(v + 1, 0, bB1);
-      DNA_BARRIER();
-      lgkm0();
-      mma(1, 0, bB0);
-      if (st) store_quadrant(c0, 1, 0);
-      if (sg) store_geglu_half(c0, 1);
-      DNA_BARRIER();
-    };
-    // prologue = the stages of the virtual steps -2 and -1: S(0,B0) S(0,A0) S(0,B1) S(0,A1)
-    // S(1,B0) S(1,A0) S(1,B1); the wait retires the two oldest, then B_0(0) is read ("phase 3
-    // of step -1")
-    stage(c0, 0, hB0);
-    stage(c0, 0, hA0);
-    stage(c0, 0, hB1);
-    stage(c0, 0, hA1);
-    stage(c1, 1, hB0);
-    stage(c1, 1, hA0);
-    stage(c1, 1, hB1);
-    __builtin_amdgcn_s_waitcnt(waitcnt_imm(10));
-    DNA_BARRIER();
-    readB(0, 0, bf0);
-    if (wr == 1) DNA_BARRIER();  // stagger: waves 4-7 one barrier behind
-    int kt = 0, i = 0;
-    auto next = [&]() {
-      advance(c1);
-      advance(c2);
-      if (++kt == KT) {
-        kt = 0;
-        ++i;
-        c0 = cur_at(i);
-      }
-    };
-    for (int v = 0; v < V; v += 2) {
-      step(v, kt, i > 0, bf0, bf1);
-      next();
-      if (v + 1 < V) {
-        step(v + 1, kt, i > 0, bf1, bf0);
-        next();
-      }
-    }
   } else {
     // SCH == 2: the SCH 0 schedule with the per-phase instruction overhead taken out of the
     // load half-phases (the half-phase in which a wave stages, waits and reads while its SIMD
@@ -1128,9 +993,9 @@ __global__ __launch_bounds__(NTHR) void gemmp_kernel(Args a) {
           const auto gy = __builtin_amdgcn_permlane16_swap(k0[1], k1[1], false, false);
           __builtin_amdgcn_raw_buffer_store_b128(u32x4{gx[0], gy[0], gx[1], gy[1]}, rAct, off, 0, 0);
         }
-        // DNA_GEMM_NT=1 (A/B): non-temporal stores. Measured (profiles/r03b): nt, sc1 and sc0 sc1
+        // a.nt (always 0): non-temporal stores. Measured (profiles/r03b): nt, sc1 and sc0 sc1
         // stores and whole-line store patterns are all slower or equal; dropping the stores
-        // (DNA_GEMM_DBG=1) saves ~3.5 us per unit at every K: the in-order vmcnt makes the
+        // (a.dbg == 1) saves ~3.5 us per unit at every K: the in-order vmcnt makes the
         // stages issued after a unit's stores wait for them
         if (a.nt) __builtin_amdgcn_raw_buffer_store_b128(o, rC, off, 0, 2);
         else __builtin_amdgcn_raw_buffer_store_b128(o, rC, off, 0, 0);
@@ -1152,14 +1017,14 @@ __global__ __launch_bounds__(NTHR) void gemmp_kernel(Args a) {
       for (int i = 0; i < 4; ++i) {
         const uint32_t off = voGB + (uint32_t)__builtin_amdgcn_readfirstlane(
                                         ((c.m0 + mq * 128 + i * 16) * gld + c.n0 + nq * 128) * 2);
-        gv[i][0] = load_b128h(rGi, (ABL & 128) ? kOOB : off);
+        gv[i][0] = load_b128h(rGi, off);
       }
       if constexpr (GELU) return;
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         const uint32_t off = voGB + (uint32_t)__builtin_amdgcn_readfirstlane(
                                         ((c.m0 + mq * 128 + i * 16) * 2 * a.F + c.n0 + nq * 128) * 2);
-        gv[i][1] = load_b128h(rGi, (ABL & 128) ? kOOB : off + a.F * 2);
+        gv[i][1] = load_b128h(rGi, off + a.F * 2);
       }
     };
     auto lgstore = [&](const LCur& c, int mq, int nq, const bf16x8 (&gv)[4][2]) __attribute__((always_inline)) {
@@ -1343,8 +1208,9 @@ struct WArgs {
   int T, Nw, Kw, tilesM, tilesN, s, KTtot;
 };
 
-template <bool IMM, int SCH = 0>
+template <int SCH>
 __global__ __launch_bounds__(NTHR) void wgradp_kernel(WArgs a) {
+  static_assert(SCH == 0 || SCH == 2, "persistent weight gradient: bodies SCH 0 and SCH 2");
   constexpr int QS = 8;
   __shared__ __attribute__((aligned(1024))) char smem[LDS_BYTES];
   const int tid = threadIdx.x, lane = tid & 63;
@@ -1414,7 +1280,7 @@ __global__ __launch_bounds__(NTHR) void wgradp_kernel(WArgs a) {
 #pragma unroll
         for (int j = 0; j < 2; ++j) acc[q][r][i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
   bf16x8 af[4][2], bf0[2][2], bf1[2][2];
-  // IMM: per-lane fragment addresses computed once; k-block / row-half steps are instruction
+  // per-lane fragment addresses computed once; k-block / row-half steps are instruction
   // immediates (4 address VALU per read group instead of 16)
   uint32_t loA[4], loB[2];
 #pragma unroll
@@ -1424,26 +1290,12 @@ __global__ __launch_bounds__(NTHR) void wgradp_kernel(WArgs a) {
   auto readA = [&](int v, int mq) {
     const char* im = img(v, mq);
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      if constexpr (IMM) {
-        read_n2(lds_addr(im) + loA[i], af[i][0], af[i][1]);
-      } else {
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk) af[i][kk] = read_n(im, kk * 32, wr * 64 + i * 16, lane);
-      }
-    }
+    for (int i = 0; i < 4; ++i) read_n2(lds_addr(im) + loA[i], af[i][0], af[i][1]);
   };
   auto readB = [&](int v, int nq, bf16x8 (&bf)[2][2]) {
     const char* im = img(v, 2 + nq);
 #pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      if constexpr (IMM) {
-        read_n2(lds_addr(im) + loB[j], bf[j][0], bf[j][1]);
-      } else {
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk) bf[j][kk] = read_n(im, kk * 32, wc * 32 + j * 16, lane);
-      }
-    }
+    for (int j = 0; j < 2; ++j) read_n2(lds_addr(im) + loB[j], bf[j][0], bf[j][1]);
   };
   auto mma = [&](int mq, int nq, const bf16x8 (&bf)[2][2]) {
     __builtin_amdgcn_s_setprio(1);
@@ -1546,99 +1398,11 @@ __global__ __launch_bounds__(NTHR) void wgradp_kernel(WArgs a) {
     }
     c0 = cur_at(i + 1);
   }
-  } else if constexpr (SCH == 1) {
-    // SCH == 1: gemmp_kernel's balanced-read schedule (reads A_0 / B_1 / A_1 / B_0(next) per
-    // phase, 5 half-tiles in flight; see there). Units have per-chunk lengths, so the current
-    // unit's last K-step starts at phase 4 * (len - 1).
-    constexpr int hA0 = 0, hA1 = 1, hB0 = 2, hB1 = 3;
-    auto wait_p = [&](auto phase, int role) {
-      constexpr int p = decltype(phase)::value;
-      if (role == 0) __builtin_amdgcn_s_waitcnt(waitcnt_imm(10));
-      else if (role == 1) __builtin_amdgcn_s_waitcnt(waitcnt_imm(10 + pend_stores<EPI_F32>(1, p)));
-      else if (role == 2) __builtin_amdgcn_s_waitcnt(waitcnt_imm(10 + pend_stores<EPI_F32>(2, p)));
-      else if (role == 3) __builtin_amdgcn_s_waitcnt(waitcnt_imm(10 + pend_stores<EPI_F32>(3, p)));
-      else __builtin_amdgcn_s_waitcnt(waitcnt_imm(10 + pend_stores<EPI_F32>(4, p)));
-    };
-    auto lgkm0 = [&]() {
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      __builtin_amdgcn_sched_barrier(0);
-    };
-    auto step = [&](int v, int kt, bool prev, bf16x8 (&bB0)[2][2], bf16x8 (&bB1)[2][2]) {
-      const bool st = kt == c0.len - 1;
-      const int role = __builtin_amdgcn_readfirstlane(
-          st ? (prev && kt == 1 ? 4 : 3) : prev && kt == 0 ? 1 : prev && kt == 1 ? 2 : 0);
-      stage(c1, v + 1, hA1);
-      wait_p(std::integral_constant<int, 0>{}, role);
-      readA(v, 0);
-      DNA_BARRIER();
-      lgkm0();
-      mma(0, 0, bB0);
-      if (st) store_quadrant(c0, 0, 0);
-      DNA_BARRIER();
-      stage(c2, v + 2, hB0);
-      wait_p(std::integral_constant<int, 1>{}, role);
-      readB(v, 1, bB1);
-      DNA_BARRIER();
-      lgkm0();
-      mma(0, 1, bB1);
-      if (st) store_quadrant(c0, 0, 1);
-      DNA_BARRIER();
-      stage(c2, v + 2, hA0);
-      wait_p(std::integral_constant<int, 2>{}, role);
-      readA(v, 1);
-      DNA_BARRIER();
-      lgkm0();
-      mma(1, 1, bB1);
-      if (st) store_quadrant(c0, 1, 1);
-      DNA_BARRIER();
-      stage(c2, v + 2, hB1);
-      wait_p(std::integral_constant<int, 3>{}, role);
-      readB(v + 1, 0, bB1);
-      DNA_BARRIER();
-      lgkm0();
-      mma(1, 0, bB0);
-      if (st) store_quadrant(c0, 1, 0);
-      DNA_BARRIER();
-    };
-    stage(c0, 0, hB0);
-    stage(c0, 0, hA0);
-    stage(c0, 0, hB1);
-    stage(c0, 0, hA1);
-    stage(c1, 1, hB0);
-    stage(c1, 1, hA0);
-    stage(c1, 1, hB1);
-    __builtin_amdgcn_s_waitcnt(waitcnt_imm(10));
-    DNA_BARRIER();
-    readB(0, 0, bf0);
-    if (wr == 1) DNA_BARRIER();
-    int kt = 0, i = 0;
-    const int V = [&]() {  // K-steps of this block's units
-      int n = 0;
-      for (int j = 0; j < nb; ++j) n += cur_at(j).len;
-      return n;
-    }();
-    auto next = [&]() {
-      advance(c1);
-      advance(c2);
-      if (++kt == c0.len) {
-        kt = 0;
-        ++i;
-        c0 = cur_at(i);
-      }
-    };
-    for (int v = 0; v < V; v += 2) {
-      step(v, kt, i > 0, bf0, bf1);
-      next();
-      if (v + 1 < V) {
-        step(v + 1, kt, i > 0, bf1, bf0);
-        next();
-      }
-    }
   } else {
     // SCH == 2: the lean form of the SCH 0 schedule (see gemmp_kernel's SCH == 2): K-steps
     // unrolled by two with compile-time buffer parity, fragment reads off per-lane base
     // registers with immediate offsets, per-unit stage offsets and buffer resources computed once
-    // per unit, compile-time wait roles. Chunks are whole K-step pairs (WArgs.pairs), so every
+    // per unit, compile-time wait roles. Chunks are whole K-step pairs (the launcher rounds KTtot up to even), so every
     // unit starts on parity 0.
     uint32_t bA[2][4], bB[2][2];
     const uint32_t sbase = lds_addr(smem);
@@ -1817,19 +1581,64 @@ __global__ __launch_bounds__(NTHR) void wgradp_kernel(WArgs a) {
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
+// ----------------------------------------------------------------------------- dispatch
+// Environment switches (benchmarks / A/B). Each selects among kernels and launch parameters that
+// the default dispatch reaches anyway; a value outside the accepted set is an error, never a quiet
+// fall-back to the default. Unset or empty means the default.
+struct Switches {
+  bool persistent;  // DNA_GEMM_P: 0 = gemm_kernel where the forward would take gemmp_kernel
+  int sched;        // DNA_GEMM_SCHED: 0 = the SCH 0 bodies where the default takes SCH 2
+  int gm;           // DNA_GEMM_GM: row tiles per column sweep; 0 = the entry point's own
+  int grid;         // DNA_GEMM_GRID: workgroups of gemmp_kernel; 0 = one per CU
+};
+
+// v as an integer >= lo that is a multiple of `mult`; dflt when unset or empty, -1 otherwise
+inline long switch_value(const char* v, long dflt, long lo, long hi, long mult) {
+  if (!v || !*v) return dflt;
+  char* end;
+  const long x = strtol(v, &end, 10);
+  return (*end == 0 && x >= lo && x <= hi && x % mult == 0) ? x : -1;
+}
+
+// The one reader: called by every entry point before its first HIP call. DNA_GEMM_P is read once
+// per process, the others per call (the in-process A/B scripts and tests change them).
+inline int read_switches(const char* fn, Switches& sw) {
+  static const std::string p_text = [](const char* v) { return std::string(v ? v : ""); }(getenv("DNA_GEMM_P"));
+  static const long p_once = switch_value(p_text.c_str(), 1, 0, 1, 1);  // a copy: later setenv cannot reach it
+  struct { const char *name, *text, *accepted; long value; } e[4] = {
+      {"DNA_GEMM_P", p_text.c_str(), "0, 1 or unset", p_once},
+      {"DNA_GEMM_SCHED", getenv("DNA_GEMM_SCHED"), "0, 2 or unset", 0},
+      {"DNA_GEMM_GM", getenv("DNA_GEMM_GM"), "an integer >= 1 or unset", 0},
+      {"DNA_GEMM_GRID", getenv("DNA_GEMM_GRID"), "a positive multiple of 8 or unset", 0}};
+  e[1].value = switch_value(e[1].text, 2, 0, 2, 2);
+  e[2].value = switch_value(e[2].text, 0, 1, 1 << 20, 1);
+  e[3].value = switch_value(e[3].text, 0, 8, 1 << 20, 8);
+  for (const auto& s : e)
+    if (s.value < 0) {
+      set_error("%s: %s=%s selects nothing (accepted: %s)", fn, s.name, s.text, s.accepted);
+      return DNA_ERR_UNSUPPORTED;
+    }
+  sw = Switches{e[0].value == 1, (int)e[1].value, (int)e[2].value, (int)e[3].value};
+  return DNA_OK;
+}
+#define DNA_READ_SWITCHES(sw, fn)                                    \
+  Switches sw;                                                       \
+  do {                                                               \
+    const int st_ = read_switches(fn, sw);                           \
+    if (st_ != DNA_OK) return st_;                                   \
+  } while (0)
+
 template <bool AK, bool BKM, int EPI>
-int launch(Args& a, int splits, hipStream_t s, const char* name) {
+int launch(Args& a, const Switches& sw, int splits, hipStream_t s, const char* name) {
   a.tilesM = (a.M + BM - 1) / BM;
   const int nper = (EPI == EPI_GEGLU ? BN / 2 : BN);
   a.tilesN = (a.N + nper - 1) / nper;
-  if (const char* e = getenv("DNA_GEMM_GM")) a.GM = atoi(e);
-  if (a.GM <= 0) a.GM = 4;
+  if (sw.gm) a.GM = sw.gm;
   dim3 grid(a.tilesM * a.tilesN, splits);
   hipLaunchKernelGGL((gemm_kernel<AK, BKM, EPI>), grid, dim3(NTHR), 0, s, a);
   DNA_LAUNCH_CHECK(name);
   return DNA_OK;
 }
-
 
 inline int num_cus() {
   static int n = 0;
@@ -1842,62 +1651,27 @@ inline int num_cus() {
   return n;
 }
 
-inline bool persistent_enabled() {
-  static int on = -1;
-  if (on < 0) {
-    const char* e = getenv("DNA_GEMM_P");
-    on = (e && e[0] == '0') ? 0 : 1;
-  }
-  return on == 1;
-}
-
-// persistent-kernel half-tile schedule (DNA_GEMM_SCHED, read per call for in-process A/B):
-// 2 (default) = the lean K-step body, 0 = the original one, 1 = balanced reads (slower)
-inline int gemm_sched() {
-  const char* e = getenv("DNA_GEMM_SCHED");
-  return e ? atoi(e) : 2;
-}
-
+// The only launch site of gemmp_kernel: tiles, sweep group, grid (one workgroup per CU, or per
+// unit when there are fewer) and body -- SCH 2 where K / 64 is even unless DNA_GEMM_SCHED=0. The
+// epilogues with a lean body only ignore the switch; their entry points check the even step count.
 template <int EPI>
-int launchp(Args& a, hipStream_t s, const char* name) {
+int launchp(Args& a, const Switches& sw, hipStream_t s, const char* name) {
   a.tilesM = (a.M + BM - 1) / BM;
   const int nper = (EPI == EPI_GEGLU ? BN / 2 : BN);
   a.tilesN = (a.N + nper - 1) / nper;
-  if (const char* e = getenv("DNA_GEMM_GM")) a.GM = atoi(e);
-  if (a.GM <= 0) a.GM = 8;
+  if (sw.gm) a.GM = sw.gm;
   const int U = a.tilesM * a.tilesN;
-  int G = num_cus();
-  if (const char* e = getenv("DNA_GEMM_GRID")) G = atoi(e);
+  int G = sw.grid ? sw.grid : num_cus();
   G = U < G ? U : (G & ~7);
-  a.rot = 0;
-  if (const char* e = getenv("DNA_GEMM_ROT")) a.rot = atoi(e);
-  a.dbg = 0;
-  if (const char* e = getenv("DNA_GEMM_DBG")) a.dbg = atoi(e);
-  a.nt = 0;
-  if (const char* e = getenv("DNA_GEMM_NT")) a.nt = atoi(e);
-  a.order = 0;
-  if (const char* e = getenv("DNA_GEMM_ORDER")) a.order = atoi(e);
-  if constexpr (EPI == EPI_BF16_GELU) {  // lean body only (K / BK even: the launcher checks)
-    hipLaunchKernelGGL((gemmp_kernel<EPI, 0, 2>), dim3(G), dim3(NTHR), 0, s, a);
-  } else {
-    const char* ab = getenv("DNA_GEMM_ABL");
-    const int abl = ab ? atoi(ab) : 0;
-    if (abl == 0 && gemm_sched() == 1) hipLaunchKernelGGL((gemmp_kernel<EPI, 0, 1>), dim3(G), dim3(NTHR), 0, s, a);
-    else if (abl == 0 && gemm_sched() == 2 && (a.K / BK) % 2 == 0)
-      hipLaunchKernelGGL((gemmp_kernel<EPI, 0, 2>), dim3(G), dim3(NTHR), 0, s, a);
-    else if (abl == 1) hipLaunchKernelGGL((gemmp_kernel<EPI, 1>), dim3(G), dim3(NTHR), 0, s, a);
-    else if (abl == 2) hipLaunchKernelGGL((gemmp_kernel<EPI, 2>), dim3(G), dim3(NTHR), 0, s, a);
-    else if (abl == 3) hipLaunchKernelGGL((gemmp_kernel<EPI, 3>), dim3(G), dim3(NTHR), 0, s, a);
-    else if (abl == 7) hipLaunchKernelGGL((gemmp_kernel<EPI, 7>), dim3(G), dim3(NTHR), 0, s, a);
-    else if (abl == 8) hipLaunchKernelGGL((gemmp_kernel<EPI, 8>), dim3(G), dim3(NTHR), 0, s, a);
-    else if (abl == 16) hipLaunchKernelGGL((gemmp_kernel<EPI, 16>), dim3(G), dim3(NTHR), 0, s, a);
-    else if (abl == 32) hipLaunchKernelGGL((gemmp_kernel<EPI, 32>), dim3(G), dim3(NTHR), 0, s, a);
-    else hipLaunchKernelGGL((gemmp_kernel<EPI>), dim3(G), dim3(NTHR), 0, s, a);
+  bool lean = true;
+  if constexpr (EPI == EPI_BF16 || EPI == EPI_GEGLU) {
+    lean = sw.sched != 0 && (a.K / BK) % 2 == 0;
+    if (!lean) hipLaunchKernelGGL((gemmp_kernel<EPI, 0>), dim3(G), dim3(NTHR), 0, s, a);
   }
+  if (lean) hipLaunchKernelGGL((gemmp_kernel<EPI, 2>), dim3(G), dim3(NTHR), 0, s, a);
   DNA_LAUNCH_CHECK(name);
   return DNA_OK;
 }
-
 
 // chunk count for dna_linear_wgrad_p: minimise the modelled time in K-step units --
 //   ceil(tiles*s / G) rounds x (KTtot/s steps + ~3 steps of per-unit store tail)
@@ -1914,14 +1688,24 @@ inline int wgrad_chunks(int tiles, int KTtot, int G, double nk) {
   return best;
 }
 
-// Row-block size for an operand past 32-bit byte offsets: the fewest blocks of at most `cap` rows
-// (cap a multiple of the 256-row tile), split as evenly as the tile allows -- so every launch
-// gets about the same unit count (a max-size-first split left the K = 6144 data gradient's second
-// launch 4.01 rounds of units: a fifth round with 2 units, ~0.1 ms of idle chip per call)
-inline int row_block(int M, int cap) {
+// The persistent kernel addresses an operand with 32-bit byte offsets, so an M-row problem runs
+// as row blocks, one launch each: fn(r0, rows) for the fewest blocks of at most `cap` rows (the
+// 256-row tiles of `widest_row_bytes`-byte rows that fit under 2^31 bytes), split as evenly as the
+// tile allows -- so every launch gets about the same unit count (a max-size-first split left the
+// K = 6144 data gradient's second launch 4.01 rounds of units: a fifth round with 2 units, ~0.1 ms
+// of idle chip per call). E.g. T = 262,144 tokens (b = 512) at N = 6144 runs as two launches of
+// the b = 256 shape. False (nothing ran, st untouched) when not even one tile of rows fits; else
+// true with st = fn's first failure or DNA_OK.
+template <typename Fn>
+bool for_row_blocks(int M, size_t widest_row_bytes, int& st, Fn fn) {
+  const int cap = (int)(((1ull << 31) - 1) / widest_row_bytes / BM * BM);
+  if (cap < BM) return false;
   const int nblk = (M + cap - 1) / cap;
   const int per = (M + nblk - 1) / nblk;
-  return (per + BM - 1) / BM * BM;
+  const int mc = (per + BM - 1) / BM * BM;
+  st = DNA_OK;
+  for (int r0 = 0; r0 < M && st == DNA_OK; r0 += mc) st = fn(r0, M - r0 < mc ? M - r0 : mc);
+  return true;
 }
 
 inline Args base_args() {
@@ -1941,33 +1725,26 @@ extern "C" int dna_linear_fwd(const void* x, const void* w, const float* bias, i
   DNA_CHECK_ARG(x && w && y, "dna_linear_fwd: null pointer");
   DNA_CHECK_ARG(M >= 0 && N > 0 && K > 0, "dna_linear_fwd: bad shape");
   DNA_CHECK_ARG(K % BK == 0 && N % 8 == 0, "dna_linear_fwd: K %% 64 and N %% 8 required (K=%d N=%d)", K, N);
+  DNA_READ_SWITCHES(sw, "dna_linear_fwd");
   if (M == 0) return DNA_OK;
   Args a = base_args();
   a.A = (const bf16*)x; a.lda = K;
   a.B = (const bf16*)w; a.ldb = K;
   a.C = y; a.ldc = N; a.bias = bias;
   a.M = M; a.N = N; a.K = K; a.ksplit = K;
-  if (persistent_enabled() && N <= BIAS_LDS / 4 && N % BN == 0 && K >= 2 * BK &&
+  if (sw.persistent && N <= BIAS_LDS / 4 && N % BN == 0 && K >= 2 * BK &&
       (size_t)N * K * 2 < (1ull << 31)) {
-    // the persistent kernel addresses an operand with 32-bit byte offsets: row blocks of at most
-    // mc rows (a multiple of the 256-row tile) per launch, so e.g. T = 262,144 tokens (b = 512)
-    // at N = 6144 runs as two launches of the b = 256 shape instead of the non-persistent kernel
-    const size_t wide = (size_t)(K > N ? K : N) * 2;
-    const int cap = (int)(((1ull << 31) - 1) / wide / BM * BM);
-    if (cap >= BM) {
-      const int mc = row_block(M, cap);
-      for (int r0 = 0; r0 < M; r0 += mc) {
-        Args c = a;
-        c.A = a.A + (size_t)r0 * K;
-        c.C = (bf16*)a.C + (size_t)r0 * N;
-        c.M = M - r0 < mc ? M - r0 : mc;
-        const int st = launchp<EPI_BF16>(c, as_stream(stream), "dna_linear_fwd");
-        if (st != DNA_OK) return st;
-      }
-      return DNA_OK;
-    }
+    int st;
+    const bool fits = for_row_blocks(M, (size_t)(K > N ? K : N) * 2, st, [&](int r0, int rows) {
+      Args c = a;
+      c.A = a.A + (size_t)r0 * K;
+      c.C = (bf16*)a.C + (size_t)r0 * N;
+      c.M = rows;
+      return launchp<EPI_BF16>(c, sw, as_stream(stream), "dna_linear_fwd");
+    });
+    if (fits) return st;
   }
-  return launch<true, true, EPI_BF16>(a, 1, as_stream(stream), "dna_linear_fwd");
+  return launch<true, true, EPI_BF16>(a, sw, 1, as_stream(stream), "dna_linear_fwd");
 }
 
 extern "C" int dna_linear_gelu_fwd(const void* x, const void* w, const float* bias, int M, int N,
@@ -1980,25 +1757,25 @@ extern "C" int dna_linear_gelu_fwd(const void* x, const void* w, const float* bi
                     (size_t)N * K * 2 < (1ull << 31),
                 "dna_linear_gelu_fwd: N %% 256 (<= %d) and K %% 128 required (N=%d K=%d)",
                 BIAS_LDS / 4, N, K);
+  DNA_READ_SWITCHES(sw, "dna_linear_gelu_fwd");
   if (M == 0) return DNA_OK;
   Args a = base_args();
   a.A = (const bf16*)x; a.lda = K;
   a.B = (const bf16*)w; a.ldb = K;
   a.C = h; a.ldc = N; a.bias = bias; a.aux = (bf16*)act;
   a.M = M; a.N = N; a.K = K; a.ksplit = K;
+  int st;
   const size_t wide = (size_t)(K > N ? K : N) * 2;
-  const int cap = (int)(((1ull << 31) - 1) / wide / BM * BM);
-  const int mc = row_block(M, cap);
-  for (int r0 = 0; r0 < M; r0 += mc) {
+  const bool fits = for_row_blocks(M, wide, st, [&](int r0, int rows) {
     Args c = a;
     c.A = a.A + (size_t)r0 * K;
     c.C = (bf16*)a.C + (size_t)r0 * N;
     c.aux = a.aux + (size_t)r0 * N;
-    c.M = M - r0 < mc ? M - r0 : mc;
-    const int st = launchp<EPI_BF16_GELU>(c, as_stream(stream), "dna_linear_gelu_fwd");
-    if (st != DNA_OK) return st;
-  }
-  return DNA_OK;
+    c.M = rows;
+    return launchp<EPI_BF16_GELU>(c, sw, as_stream(stream), "dna_linear_gelu_fwd");
+  });
+  DNA_CHECK_ARG(fits, "dna_linear_gelu_fwd: rows of %zu bytes exceed 32-bit offsets", wide);
+  return st;
 }
 
 extern "C" int dna_linear_dgrad(const void* dy, const void* w, int M, int N, int K, void* dx,
@@ -2006,13 +1783,14 @@ extern "C" int dna_linear_dgrad(const void* dy, const void* w, int M, int N, int
   DNA_CHECK_ARG(dy && w && dx, "dna_linear_dgrad: null pointer");
   DNA_CHECK_ARG(M >= 0 && N > 0 && K > 0, "dna_linear_dgrad: bad shape");
   DNA_CHECK_ARG(N % BK == 0 && K % 8 == 0, "dna_linear_dgrad: N %% 64 and K %% 8 required (N=%d K=%d)", N, K);
+  DNA_READ_SWITCHES(sw, "dna_linear_dgrad");
   if (M == 0) return DNA_OK;
   Args a = base_args();
   a.A = (const bf16*)dy; a.lda = N;
   a.B = (const bf16*)w; a.ldb = K;
   a.C = dx; a.ldc = K;
   a.M = M; a.N = K; a.K = N; a.ksplit = N;
-  return launch<true, false, EPI_BF16>(a, 1, as_stream(stream), "dna_linear_dgrad");
+  return launch<true, false, EPI_BF16>(a, sw, 1, as_stream(stream), "dna_linear_dgrad");
 }
 
 extern "C" int dna_linear_wgrad(const void* dy, const void* x, int M, int N, int K, int splits,
@@ -2021,13 +1799,14 @@ extern "C" int dna_linear_wgrad(const void* dy, const void* x, int M, int N, int
   DNA_CHECK_ARG(M > 0 && N > 0 && K > 0 && splits > 0, "dna_linear_wgrad: bad shape");
   DNA_CHECK_ARG(M % (splits * BK) == 0, "dna_linear_wgrad: rows %d not a multiple of 64*splits", M);
   DNA_CHECK_ARG(N % 8 == 0 && K % 8 == 0, "dna_linear_wgrad: N, K %% 8 required");
+  DNA_READ_SWITCHES(sw, "dna_linear_wgrad");
   Args a = base_args();
   a.A = (const bf16*)dy; a.lda = N;   // A[k=token][m=out feature]
   a.B = (const bf16*)x; a.ldb = K;    // B[k=token][n=in feature]
   a.C = partials; a.ldc = K;
   a.M = N; a.N = K; a.K = M; a.ksplit = M / splits;
   a.GM = 2;
-  return launch<false, false, EPI_F32>(a, splits, as_stream(stream), "dna_linear_wgrad");
+  return launch<false, false, EPI_F32>(a, sw, splits, as_stream(stream), "dna_linear_wgrad");
 }
 
 extern "C" int dna_geglu_linear_fwd(const void* x, const void* w, const float* bias, int M, int F,
@@ -2038,6 +1817,7 @@ extern "C" int dna_geglu_linear_fwd(const void* x, const void* w, const float* b
   DNA_CHECK_ARG(M >= 0 && K % BK == 0 && F % (BN / 2) == 0,
                 "dna_geglu_linear_fwd: K %% 64 and F %% 128 required (K=%d F=%d)", K, F);
   DNA_CHECK_ARG(p_drop >= 0.f && p_drop < 1.f, "dna_geglu_linear_fwd: bad p");
+  DNA_READ_SWITCHES(sw, "dna_geglu_linear_fwd");
   if (M == 0) return DNA_OK;
   Args a = base_args();
   a.A = (const bf16*)x; a.lda = K;
@@ -2046,26 +1826,20 @@ extern "C" int dna_geglu_linear_fwd(const void* x, const void* w, const float* b
   a.M = M; a.N = F; a.K = K; a.ksplit = K; a.F = F;
   a.p = p_drop; a.th = dropout_threshold16(p_drop); a.ks = 1.f / (1.f - p_drop);
   a.seed = seed; a.off = offset;
-  if (persistent_enabled() && 2 * F <= BIAS_LDS / 4 && K >= 2 * BK && (size_t)2 * F * K * 2 < (1ull << 31)) {
-    // 32-bit byte offsets: row blocks of at most mc rows per launch (see dna_linear_fwd)
-    const size_t wide = (size_t)(K > 2 * F ? K : 2 * F) * 2;
-    const int cap = (int)(((1ull << 31) - 1) / wide / BM * BM);
-    if (cap >= BM) {
-      const int mc = row_block(M, cap);
-      for (int r0 = 0; r0 < M; r0 += mc) {
-        Args c = a;
-        c.A = a.A + (size_t)r0 * K;
-        c.C = (bf16*)a.C + (size_t)r0 * 2 * F;
-        c.aux = a.aux + (size_t)r0 * F;
-        c.M = M - r0 < mc ? M - r0 : mc;
-        c.off = a.off + (uint64_t)r0 * F / 8;  // dropout groups of 8 elements, row-major
-        const int st = launchp<EPI_GEGLU>(c, as_stream(stream), "dna_geglu_linear_fwd");
-        if (st != DNA_OK) return st;
-      }
-      return DNA_OK;
-    }
+  if (sw.persistent && 2 * F <= BIAS_LDS / 4 && K >= 2 * BK && (size_t)2 * F * K * 2 < (1ull << 31)) {
+    int st;
+    const bool fits = for_row_blocks(M, (size_t)(K > 2 * F ? K : 2 * F) * 2, st, [&](int r0, int rows) {
+      Args c = a;
+      c.A = a.A + (size_t)r0 * K;
+      c.C = (bf16*)a.C + (size_t)r0 * 2 * F;
+      c.aux = a.aux + (size_t)r0 * F;
+      c.M = rows;
+      c.off = a.off + (uint64_t)r0 * F / 8;  // dropout groups of 8 elements, row-major
+      return launchp<EPI_GEGLU>(c, sw, as_stream(stream), "dna_geglu_linear_fwd");
+    });
+    if (fits) return st;
   }
-  return launch<true, true, EPI_GEGLU>(a, 1, as_stream(stream), "dna_geglu_linear_fwd");
+  return launch<true, true, EPI_GEGLU>(a, sw, 1, as_stream(stream), "dna_geglu_linear_fwd");
 }
 
 extern "C" int dna_geglu_linear_dgrad(const void* dy, const void* w, const void* fac, int M, int F,
@@ -2074,13 +1848,14 @@ extern "C" int dna_geglu_linear_dgrad(const void* dy, const void* w, const void*
   const void* g = fac;
   DNA_CHECK_ARG(M >= 0 && N % BK == 0 && F % 8 == 0,
                 "dna_geglu_linear_dgrad: hidden %% 64 and F %% 8 required (N=%d F=%d)", N, F);
+  DNA_READ_SWITCHES(sw, "dna_geglu_linear_dgrad");
   if (M == 0) return DNA_OK;
   Args a = base_args();
   a.A = (const bf16*)dy; a.lda = N;
   a.B = (const bf16*)w; a.ldb = F;
   a.C = nullptr; a.ldc = F; a.g = (const bf16*)g; a.aux = (bf16*)dg;
   a.M = M; a.N = F; a.K = N; a.ksplit = N; a.F = F;
-  return launch<true, false, EPI_GEGLU_BWD>(a, 1, as_stream(stream), "dna_geglu_linear_dgrad");
+  return launch<true, false, EPI_GEGLU_BWD>(a, sw, 1, as_stream(stream), "dna_geglu_linear_dgrad");
 }
 
 // dg[M, 2F] = bf16(dy[M, N] . Wt[F, N]^T) * fac on the persistent kernel: the data gradient of
@@ -2095,38 +1870,26 @@ extern "C" int dna_geglu_linear_dgrad_p(const void* dy, const void* wt, const vo
                 "dna_geglu_linear_dgrad_p: hidden %% 128 and F %% 256 required (N=%d F=%d)", N, F);
   const void* g = fac;
   DNA_CHECK_ARG((size_t)F * N * 2 < (1ull << 31), "dna_geglu_linear_dgrad_p: weight too large");
+  DNA_READ_SWITCHES(sw, "dna_geglu_linear_dgrad_p");
   if (M == 0) return DNA_OK;
   Args a = base_args();
   a.A = (const bf16*)dy; a.lda = N;
   a.B = (const bf16*)wt; a.ldb = N;
   a.C = nullptr; a.ldc = 2 * F; a.g = (const bf16*)g; a.aux = (bf16*)dg;
   a.N = F; a.K = N; a.ksplit = N; a.F = F;
-  // DNA_GEMM_ABL=128 (timing-only diagnostic, results invalid): the epilogue without the
-  // factor loads
-  const char* ab = getenv("DNA_GEMM_ABL");
-  const int abl = ab ? atoi(ab) : 0;
-  a.tilesN = F / BN;
   a.GM = 8;
-  if (const char* e = getenv("DNA_GEMM_GM")) a.GM = atoi(e);
   const size_t wide = (size_t)(N > 2 * F ? N : 2 * F) * 2;
-  const int cap = (int)(((1ull << 31) - 1) / wide / BM * BM);
-  DNA_CHECK_ARG(cap >= BM, "dna_geglu_linear_dgrad_p: rows of %zu bytes exceed 32-bit offsets", wide);
-  const int mc = row_block(M, cap);
-  for (int r0 = 0; r0 < M; r0 += mc) {
+  int st;
+  const bool fits = for_row_blocks(M, wide, st, [&](int r0, int rows) {
     Args c = a;
     c.A = a.A + (size_t)r0 * N;
     c.g = a.g + (size_t)r0 * 2 * F;
     c.aux = a.aux + (size_t)r0 * 2 * F;
-    c.M = M - r0 < mc ? M - r0 : mc;
-    c.tilesM = (c.M + BM - 1) / BM;
-    const int U = c.tilesM * c.tilesN;
-    int G = num_cus();
-    G = U < G ? U : (G & ~7);
-    if (abl == 128) hipLaunchKernelGGL((gemmp_kernel<EPI_GEGLU_BWD, 128, 2>), dim3(G), dim3(NTHR), 0, as_stream(stream), c);
-    else hipLaunchKernelGGL((gemmp_kernel<EPI_GEGLU_BWD, 0, 2>), dim3(G), dim3(NTHR), 0, as_stream(stream), c);
-    DNA_LAUNCH_CHECK("dna_geglu_linear_dgrad_p");
-  }
-  return DNA_OK;
+    c.M = rows;
+    return launchp<EPI_GEGLU_BWD>(c, sw, as_stream(stream), "dna_geglu_linear_dgrad_p");
+  });
+  DNA_CHECK_ARG(fits, "dna_geglu_linear_dgrad_p: rows of %zu bytes exceed 32-bit offsets", wide);
+  return st;
 }
 
 // dh = gelu_tanh'(h) * (dy . W) for the Mlp's fc2 (HyenaDNA Block, flash_attn Mlp with
@@ -2138,6 +1901,7 @@ extern "C" int dna_gelu_linear_dgrad_p(const void* dy, const void* wt, const voi
   DNA_CHECK_ARG(M >= 0 && N % BK == 0 && (N / BK) % 2 == 0 && N >= 2 * BK && F % BN == 0,
                 "dna_gelu_linear_dgrad_p: N %% 128 and F %% 256 required (N=%d F=%d)", N, F);
   DNA_CHECK_ARG((size_t)F * N * 2 < (1ull << 31), "dna_gelu_linear_dgrad_p: weight too large");
+  DNA_READ_SWITCHES(sw, "dna_gelu_linear_dgrad_p");
   if (M == 0) return DNA_OK;
   Args a = base_args();
   a.A = (const bf16*)dy; a.lda = N;
@@ -2145,27 +1909,19 @@ extern "C" int dna_gelu_linear_dgrad_p(const void* dy, const void* wt, const voi
   a.C = nullptr; a.ldc = F; a.g = (const bf16*)h; a.aux = (bf16*)dh;
   a.N = F; a.K = N; a.ksplit = N; a.F = F;
   a.p = 0.f;
-  a.tilesN = F / BN;
   a.GM = 8;
-  if (const char* e = getenv("DNA_GEMM_GM")) a.GM = atoi(e);
   const size_t wide = (size_t)(N > F ? N : F) * 2;
-  const int cap = (int)(((1ull << 31) - 1) / wide / BM * BM);
-  DNA_CHECK_ARG(cap >= BM, "dna_gelu_linear_dgrad_p: rows of %zu bytes exceed 32-bit offsets", wide);
-  const int mc = row_block(M, cap);
-  for (int r0 = 0; r0 < M; r0 += mc) {
+  int st;
+  const bool fits = for_row_blocks(M, wide, st, [&](int r0, int rows) {
     Args c = a;
     c.A = a.A + (size_t)r0 * N;
     c.g = a.g + (size_t)r0 * F;
     c.aux = a.aux + (size_t)r0 * F;
-    c.M = M - r0 < mc ? M - r0 : mc;
-    c.tilesM = (c.M + BM - 1) / BM;
-    const int U = c.tilesM * c.tilesN;
-    int G = num_cus();
-    G = U < G ? U : (G & ~7);
-    hipLaunchKernelGGL((gemmp_kernel<EPI_GELU_BWD, 0, 2>), dim3(G), dim3(NTHR), 0, as_stream(stream), c);
-    DNA_LAUNCH_CHECK("dna_gelu_linear_dgrad_p");
-  }
-  return DNA_OK;
+    c.M = rows;
+    return launchp<EPI_GELU_BWD>(c, sw, as_stream(stream), "dna_gelu_linear_dgrad_p");
+  });
+  DNA_CHECK_ARG(fits, "dna_gelu_linear_dgrad_p: rows of %zu bytes exceed 32-bit offsets", wide);
+  return st;
 }
 
 extern "C" int dna_linear_wgrad_p_splits(int M, int N, int K) {
@@ -2183,6 +1939,7 @@ extern "C" int dna_linear_wgrad_p(const void* dy, const void* x, int M, int N, i
   DNA_CHECK_ARG((size_t)((KTtot + splits - 1) / splits) * BK * (N > K ? N : K) * 2 < (1ull << 31) &&
                     (size_t)splits * N * K * 4 < (1ull << 32),
                 "dna_linear_wgrad_p: chunks / partials too large for 32-bit buffer offsets");
+  DNA_READ_SWITCHES(sw, "dna_linear_wgrad_p");
   WArgs a{};
   a.dy = (const bf16*)dy; a.ldy = N;
   a.x = (const bf16*)x; a.ldx = K;
@@ -2192,22 +1949,18 @@ extern "C" int dna_linear_wgrad_p(const void* dy, const void* x, int M, int N, i
   const int U = a.tilesM * a.tilesN * splits;
   int G = num_cus() & ~7;
   G = U < G ? U : G;
-  const char* ie = getenv("DNA_WGRAD_IMM");  // A/B: 0 = per-read address VALU
   // the lean kernel works in K-step pairs: an odd step count (e.g. the MLM head's masked rows)
-  // gets one more step past T, which reads zeros (rows past T lie outside the chunk resources)
+  // gets one more step past T, which reads zeros (rows past T lie outside the chunk resources);
+  // where whole pairs would push a chunk past 2^31 bytes, the un-paired SCH 0 body runs
   const int KTe = KTtot + (KTtot & 1);
   const bool pairs_ok = KTe / 2 / splits >= 1 &&
                         (size_t)((KTe / 2 + splits - 1) / splits) * 2 * BK * (N > K ? N : K) * 2 < (1ull << 31);
-  if (gemm_sched() == 2 && pairs_ok && (!ie || atoi(ie) != 0)) {
+  if (sw.sched != 0 && pairs_ok) {
     a.KTtot = KTe;
-    hipLaunchKernelGGL((wgradp_kernel<true, 2>), dim3(G), dim3(NTHR), 0, as_stream(stream), a);
+    hipLaunchKernelGGL(wgradp_kernel<2>, dim3(G), dim3(NTHR), 0, as_stream(stream), a);
+  } else {
+    hipLaunchKernelGGL(wgradp_kernel<0>, dim3(G), dim3(NTHR), 0, as_stream(stream), a);
   }
-  else if (gemm_sched() == 1 && (!ie || atoi(ie) != 0))
-    hipLaunchKernelGGL((wgradp_kernel<true, 1>), dim3(G), dim3(NTHR), 0, as_stream(stream), a);
-  else if (!ie || atoi(ie) != 0)
-    hipLaunchKernelGGL(wgradp_kernel<true>, dim3(G), dim3(NTHR), 0, as_stream(stream), a);
-  else
-    hipLaunchKernelGGL(wgradp_kernel<false>, dim3(G), dim3(NTHR), 0, as_stream(stream), a);
   DNA_LAUNCH_CHECK("dna_linear_wgrad_p");
   return DNA_OK;
 }

@@ -1,6 +1,6 @@
-"""A/B of the fused wo-dgrad + GeGLU-backward kernel variants (DNA_GEGLU_BWD_VAR) at the bench
-shape (T = 262,144, F = 3072, hidden 768), interleaved rounds, vs the separate pair; one JSON
-line per (variant, round)."""
+"""A/B of the fused wo-dgrad + GeGLU-backward kernel (dna_geglu_linear_dgrad_p) at the bench
+shape (T = 262,144, F = 3072, hidden 768) against the separate pair and the bare GEMM,
+interleaved rounds; one JSON line per (variant, round)."""
 import json
 import os
 import sys
@@ -34,17 +34,9 @@ def main():
         N.call("dna_linear_fwd", dy.data_ptr(), wt.data_ptr(), None, T, F, H, da.data_ptr(), s)
         N.call("dna_geglu_bwd", da.data_ptr(), g.data_ptr(), 1, T, F, dg.data_ptr(), s)
 
-    variants = [v for v in os.environ.get("VARS", "0").split(",") if v]
     iters = int(os.environ.get("ITERS", "20"))
     for rnd in range(int(os.environ.get("ROUNDS", "3"))):
-        for v in variants + ["pair", "gemm"]:
-            fn = {"pair": pair, "gemm": gemm}.get(v, fused)
-            os.environ["DNA_GEMM_ABL"] = "0"
-            os.environ["DNA_GEGLU_BWD_SCHED"] = "2"
-            if v.startswith("s"):  # s4: the deferred-epilogue schedule
-                os.environ["DNA_GEGLU_BWD_SCHED"] = v[1:]
-            elif v not in ("pair", "gemm"):
-                os.environ["DNA_GEMM_ABL"] = v  # 0 = the real kernel, 64 / 128 diagnostics
+        for v, fn in (("fused", fused), ("pair", pair), ("gemm", gemm)):
             for _ in range(3):
                 fn()
             a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)

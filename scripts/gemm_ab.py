@@ -2,7 +2,7 @@
 """Interleaved in-process A/B of GEMM kernel variants selected by environment variables (read by
 the C ABI at every launch), at the DNABERT-2 projection shapes. Random uniform [-0.5, 0.5).
 
-  python scripts/gemm_ab.py --variants "DNA_GEMM_ROT=0;DNA_GEMM_ROT=1" --shapes fwd:2304x768
+  python scripts/gemm_ab.py --variants "DNA_GEMM_SCHED=2;DNA_GEMM_SCHED=0" --shapes fwd:2304x768
 Shapes: MODE:NxK with MODE fwd (x[M,K] . W[N,K]^T) or geglu (F x K, fused GeGLU epilogue)."""
 import argparse
 import os

@@ -5,7 +5,7 @@ weight, as functional.Linear runs it), weight gradient (the default wgrad path a
 the hand-written one), each beside hipBLASLt (torch.mm) on the same operands. Env variants
 (name=ENV=VAL,...) are interleaved in one process (rule: A/B in one process).
 
-    python scripts/gemm_shapes.py [--batch 512] [--iters 20] [--variants 'base;order=DNA_GEMM_ORDER=1']
+    python scripts/gemm_shapes.py [--batch 512] [--iters 20] [--variants 'base;sched0=DNA_GEMM_SCHED=0']
 """
 import argparse
 import json

@@ -13,16 +13,19 @@ measured) covers realistic randn data. Every output is the head of a NaN-filled 
 operand the head of a NaN-filled parent: rows past the logical end must be neither read into the
 result nor written.
 
-Dispatch (read from the launchers at the end of gemm.hip; no DNA_GEMM_* / DNA_WGRAD_* switch is
-set, so this is what the defaults reach -- _fwd_path restates the condition and every forward
-test asserts the path its shape list is named for):
-  dna_linear_fwd / dna_geglu_linear_fwd   persistent gemmp_kernel iff N % 256 == 0 (GeGLU: any F
-      % 128), N (2F) <= 8192, K >= 128 and the weight < 2 GB; body SCH = 2 iff K / 64 is even,
-      else the older SCH = 0 body; otherwise gemm_kernel<true, true, EPI>
+Dispatch (read from the launchers at the end of gemm.hip; unless a test says so no DNA_GEMM_*
+switch is set, so this is what the defaults reach -- _fwd_path restates the condition and every
+forward test asserts the path its shape list is named for):
+  dna_linear_fwd / dna_geglu_linear_fwd   persistent gemmp_kernel<EPI, SCH> iff N % 256 == 0
+      (GeGLU: any F % 128), N (2F) <= 8192, K >= 128 and the weight < 2 GB; body SCH = 2 iff
+      K / 64 is even, else the older SCH = 0 body; otherwise gemm_kernel<true, true, EPI>
   dna_linear_dgrad / dna_geglu_linear_dgrad   always gemm_kernel<true, false, EPI>
   dna_linear_wgrad                            always gemm_kernel<false, false, EPI_F32>
-  dna_geglu_linear_dgrad_p / dna_gelu_linear_dgrad_p   always gemmp_kernel<EPI, 0, 2>
-  dna_linear_wgrad_p                          wgradp_kernel<true, 2> (K-step pairs)
+  dna_geglu_linear_dgrad_p / dna_gelu_linear_dgrad_p   always gemmp_kernel<EPI, 2>
+  dna_linear_wgrad_p                          wgradp_kernel<2> (K-step pairs); wgradp_kernel<0>
+      only where a chunk of whole pairs would pass 2^31 bytes
+DNA_GEMM_SCHED=0 (read per call) puts the SCH = 0 bodies of gemmp_kernel and wgradp_kernel where
+the defaults take SCH = 2: the "sched0" / sched="0" arms run them under the same exact checks.
 """
 import pytest
 import torch
@@ -146,13 +149,14 @@ def _f32_bound(a64, b64, T):
     return a64 @ b64, (T + 2) * 2.0 ** -23 * (a64.abs() @ b64.abs())
 
 
-def _fwd_path(Nn, K, wide=None):
+def _fwd_path(Nn, K, wide=None, sched=None):
     """The launcher's choice for dna_linear_fwd (wide = 2F for dna_geglu_linear_fwd, which has no
     N % 256 condition): 'p2' / 'p0' = persistent gemmp_kernel with the SCH = 2 / SCH = 0 body,
-    'np' = gemm_kernel."""
+    'np' = gemm_kernel. sched = the value of DNA_GEMM_SCHED (None: unset, which means 2)."""
+    assert sched in (None, "0", "2")
     rows = Nn if wide is None else wide
     ok = rows <= 8192 and K >= 128 and rows * K * 2 < 2 ** 31 and (wide is not None or Nn % 256 == 0)
-    return "np" if not ok else ("p2" if (K // 64) % 2 == 0 else "p0")
+    return "np" if not ok else ("p2" if sched != "0" and (K // 64) % 2 == 0 else "p0")
 
 
 # ------------------------------------------------------------------ device plumbing
@@ -229,6 +233,9 @@ FWD_NP = ([(M, 256, 64) for M in (1, 257, 600)] +
           [(M, Nn, K) for Nn in (8, 264, 1000) for K in (64, 192) for M in (1, 257, 600)])
 FWD_ALL = [(p, s) for p, shapes in (("p2", FWD_P2), ("p0", FWD_P0), ("np", FWD_NP)) for s in shapes]
 FWD_IDS = [f"{p}-{M}x{Nn}x{K}" for p, (M, Nn, K) in FWD_ALL]
+# the exact test also runs the SCH = 0 body at even K / 64, where only DNA_GEMM_SCHED=0 reaches it
+FWD_EXACT = FWD_ALL + [("sched0", s) for s in FWD_P2]
+FWD_EXACT_IDS = [f"{p}-{M}x{Nn}x{K}" for p, (M, Nn, K) in FWD_EXACT]
 # (M, N, K): dx[M, K] = dy[M, N] . w[N, K], N / 64 K-steps = 1, 3, 12, 1 and (added) 2
 DGRAD = [(1, 64, 8), (257, 192, 264), (600, 768, 1000), (300, 64, 256), (129, 128, 72)]
 WGRAD_NK = [(8, 8), (264, 136), (256, 256)]
@@ -236,8 +243,8 @@ WGRAD_P_NK = [(256, 256), (512, 256)]
 WGRAD_P_T = (128, 129, 191, 192, 193, 640, 1000)
 
 
-def _check_path(path, M, Nn, K):
-    assert _fwd_path(Nn, K) == path
+def _check_path(path, M, Nn, K, sched=None):
+    assert _fwd_path(Nn, K, sched=sched) == path
     if M == MANY_M:
         G = torch.cuda.get_device_properties(0).multi_processor_count & ~7
         U = ((M + 255) // 256) * (Nn // 256)
@@ -247,12 +254,17 @@ def _check_path(path, M, Nn, K):
 # ------------------------------------------------------------------ 2. exact root kernels
 @pytest.mark.parametrize("cls", list(CLASSES))
 @pytest.mark.parametrize("bias", [True, False], ids=["bias", "nobias"])
-@pytest.mark.parametrize("path,shape", FWD_ALL, ids=FWD_IDS)
-def test_linear_fwd_exact(path, shape, bias, cls):
+@pytest.mark.parametrize("path,shape", FWD_EXACT, ids=FWD_EXACT_IDS)
+def test_linear_fwd_exact(path, shape, bias, cls, monkeypatch):
     """dna_linear_fwd on integer operands equals bf16(exact sum + bias) everywhere; without a
-    bias the rows of x carry random scales 2^-8 .. 2^8."""
+    bias the rows of x carry random scales 2^-8 .. 2^8. The "sched0" arm sets DNA_GEMM_SCHED=0:
+    the SCH = 0 body on the even-K/64 shapes."""
     M, Nn, K = shape
-    _check_path(path, M, Nn, K)
+    if path == "sched0":
+        monkeypatch.setenv("DNA_GEMM_SCHED", "0")
+        _check_path("p0", M, Nn, K, sched="0")
+    else:
+        _check_path(path, M, Nn, K)
     g = _gen(M, Nn, K, bias, cls == "b_wide")
     amax, bmax = CLASSES[cls]
     rexp = None if bias else torch.randint(-8, 9, (M,), generator=g)
@@ -302,13 +314,33 @@ def _wgrad_p_splits(T, Nn, K):
     return sorted({auto} | {s for s in (1, 2, 3) if ((T + 63) // 64) // s >= 2})
 
 
-@pytest.mark.parametrize("cls", list(CLASSES))
-@pytest.mark.parametrize("T", WGRAD_P_T)
-@pytest.mark.parametrize("Nn,K", WGRAD_P_NK)
-def test_linear_wgrad_p_exact(Nn, K, T, cls):
-    """dna_linear_wgrad_p (wgradp_kernel in K-step pairs): odd and even step counts, T no multiple
+def _set_sched(monkeypatch, sched):
+    """sched "2" is the default (variable unset); "0" selects the un-paired SCH = 0 bodies."""
+    assert sched in ("0", "2")
+    if sched == "0":
+        monkeypatch.setenv("DNA_GEMM_SCHED", "0")
+    else:
+        monkeypatch.delenv("DNA_GEMM_SCHED", raising=False)
+
+
+def _sched_cases(*axes):
+    """parametrize arguments: the product of `axes` (first axis fastest) under sched "2" and "0".
+    The default keeps the plain id, the other arm appends -sched0."""
+    cases = [()]
+    for ax in reversed(axes):
+        cases = [(v if isinstance(v, tuple) else (v,)) + c for c in cases for v in ax]
+    vals = [c + (s,) for s in ("2", "0") for c in cases]
+    ids = ["-".join(map(str, c)) + ("" if s == "2" else "-sched0") for s in ("2", "0") for c in cases]
+    return dict(argvalues=vals, ids=ids)
+
+
+@pytest.mark.parametrize("Nn,K,T,cls,sched", **_sched_cases(WGRAD_P_NK, WGRAD_P_T, list(CLASSES)))
+def test_linear_wgrad_p_exact(Nn, K, T, cls, sched, monkeypatch):
+    """dna_linear_wgrad_p (sched "2": wgradp_kernel<2> in K-step pairs; "0": wgradp_kernel<0>, by
+    default reached only past 2^31-byte chunks): odd and even step counts, T no multiple
     of 64, the smallest legal T, the library's chunk count and forced ones; the token rows past T
     that the pair kernel's last step covers lie in NaN-filled memory and must read as zeros."""
+    _set_sched(monkeypatch, sched)
     g = _gen(Nn, K, T, cls == "b_wide", 3)
     amax, bmax = CLASSES[cls]
     dy, x = _head(_int_operand(T, Nn, amax, g)), _head(_int_operand(T, K, bmax, g))
@@ -431,9 +463,9 @@ def test_linear_wgrad_randn_elementwise(Nn, K, splits, steps):
                    what=f"dna_linear_wgrad M={M} N={Nn} K={K} splits={splits}")
 
 
-@pytest.mark.parametrize("T", WGRAD_P_T)
-@pytest.mark.parametrize("Nn,K", WGRAD_P_NK)
-def test_linear_wgrad_p_randn_elementwise(Nn, K, T):
+@pytest.mark.parametrize("Nn,K,T,sched", **_sched_cases(WGRAD_P_NK, WGRAD_P_T))
+def test_linear_wgrad_p_randn_elementwise(Nn, K, T, sched, monkeypatch):
+    _set_sched(monkeypatch, sched)
     g = _gen(Nn, K, T, 9)
     dy = _head(torch.randn(T, Nn, generator=g).bfloat16())
     x = _head(torch.randn(T, K, generator=g).bfloat16())

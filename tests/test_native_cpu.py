@@ -77,6 +77,60 @@ def test_attention_env_switch_without_a_kernel_is_an_error(fn, var, value):
     assert f"{var}={value}" in msg and "accepted" in msg, msg
 
 
+_GEMM_ENV_CHILD = """
+import ctypes, sys
+from dna_amd import _native as N
+L = N.lib()
+buf = (ctypes.c_char * (1 << 16))()  # host memory: the call must fail before anything reads it
+p = ctypes.addressof(buf)
+fn = sys.argv[1]
+if fn == "dna_linear_fwd":
+    st = L.dna_linear_fwd(p, p, None, 256, 256, 128, p, None)
+elif fn == "dna_linear_wgrad_p":
+    st = L.dna_linear_wgrad_p(p, p, 256, 256, 256, 1, p, None)
+else:
+    st = L.dna_geglu_linear_fwd(p, p, None, 256, 128, 128, 0.0, 0, 0, p, p, None)
+print(st)
+print(N.last_error())
+"""
+
+
+def _gemm_env_child(fn, var, value):
+    import subprocess
+    import sys
+    env = dict(os.environ, HIP_VISIBLE_DEVICES="-1", CUDA_VISIBLE_DEVICES="-1")
+    env[var] = value
+    r = subprocess.run([sys.executable, "-c", _GEMM_ENV_CHILD, fn], cwd=ROOT, env=env,
+                       capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr
+    status, _, msg = r.stdout.strip().partition("\n")
+    return int(status), msg
+
+
+@pytest.mark.parametrize("fn,var,value", [("dna_linear_fwd", "DNA_GEMM_SCHED", "1"),
+                                          ("dna_linear_fwd", "DNA_GEMM_SCHED", "3"),
+                                          ("dna_linear_wgrad_p", "DNA_GEMM_SCHED", "1"),
+                                          ("dna_linear_fwd", "DNA_GEMM_GRID", "4"),
+                                          ("dna_linear_fwd", "DNA_GEMM_GM", "0"),
+                                          ("dna_geglu_linear_fwd", "DNA_GEMM_P", "2")])
+def test_gemm_env_switch_with_an_unaccepted_value_is_an_error(fn, var, value):
+    """No quiet fall-back: a DNA_GEMM_* value outside the accepted set (the removed balanced-read
+    schedule, a grid that rounds down to no workgroup, anything unrecognised) fails the call,
+    before the first HIP call, with the variable and the accepted values named. The GPU is hidden
+    from the child so that the dummy host buffers can never reach a kernel."""
+    status, msg = _gemm_env_child(fn, var, value)
+    assert status == 3, (status, msg)  # DNA_ERR_UNSUPPORTED
+    assert f"{var}={value}" in msg and "accepted" in msg, msg
+
+
+def test_gemm_removed_env_switch_is_not_read():
+    """DNA_GEMM_ABL selected timing-only kernels that no longer exist; the variable is not read
+    any more, so setting it is no error of the switch reader (the call then gets as far as the
+    launch, which fails for want of a device)."""
+    status, msg = _gemm_env_child("dna_linear_fwd", "DNA_GEMM_ABL", "2")
+    assert status != 3 and "DNA_GEMM_ABL" not in msg, (status, msg)
+
+
 def test_cpp_bpe_full_encode_bit_exact():
     from dna_amd.tokenizer import DNABertTokenizer
     tok = DNABertTokenizer()
