@@ -1072,6 +1072,22 @@ extern "C" size_t dna_fftconv_kspec_elems(int L) {
   return (size_t)2 << g.logN;  // floats per channel (complex N)
 }
 
+// Host only: the geometry and instantiation the launchers above take for L, from the functions
+// they call. out[7] = logN, logM1, logM2, fixed_ln, log2 of the column / row / backward-row group.
+extern "C" int dna_fftconv_plan(int L, int* out) {
+  Geo g;
+  DNA_CHECK_ARG(out, "dna_fftconv_plan: null pointer");
+  DNA_CHECK_ARG(geometry(L, g), "dna_fftconv_plan: L=%d must be a power of 2 in [64, 131072]", L);
+  out[0] = g.logN;
+  out[1] = g.logM1;
+  out[2] = g.logM2;
+  out[3] = fixed_ln(g);
+  out[4] = log_col_group(g);
+  out[5] = log_row_group(g);
+  out[6] = log_rowbwd_group(g);
+  return DNA_OK;
+}
+
 extern "C" int dna_fftconv_filter(const float* k, const float* bias, int D, int L, int bidirectional,
                                   void* kspec, void* ws, size_t ws_bytes, void* stream) {
   Geo g;

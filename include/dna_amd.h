@@ -26,8 +26,9 @@ extern "C" {
 /* Counts additions that leave every version-1 entry point as it was (a caller built against an
  * earlier revision keeps working): 1 = dna_lm_head_*, 2 = dna_lm_head_rc_*, 3 = dna_attn_varlen_*,
  * 4 = dna_dconv_* / dna_onehot_conv_*, 5 = dna_selective_scan_plan, 6 = dna_lm_head_bias_* and
- * DNA_ACT_RELU in dna_onehot_conv_*, 7 = dna_char_batch, 8 = dna_genome_windows. */
-#define DNA_AMD_ABI_REVISION 8
+ * DNA_ACT_RELU in dna_onehot_conv_*, 7 = dna_char_batch, 8 = dna_genome_windows,
+ * 9 = dna_fftconv_plan. */
+#define DNA_AMD_ABI_REVISION 9
 
 enum dna_status {
   DNA_OK = 0,
@@ -446,6 +447,11 @@ int dna_gelu_linear_dgrad_p(const void* dy, const void* wt, const void* h, int M
  * take no bias). Its workspace: ceil(D/2) * 2L complex64; dna_fftconv_workspace(1, D, L) is enough. */
 size_t dna_fftconv_workspace(int B, int D, int L);
 size_t dna_fftconv_kspec_elems(int L);
+/* Host only, no GPU work: the transform geometry and kernel instantiation the calls below take for
+ * L. out[7] = log2 N (N = 2L = M1 * M2), log2 M1, log2 M2, fixed_ln (16 / 17 / 18: the kernels
+ * compiled for that log2 N; 0: the generic ones), then log2 of the columns per block of the column
+ * passes, of the rows per block of the row pass and of the backward's row pass. */
+int dna_fftconv_plan(int L, int* out);
 int dna_fftconv_filter(const float* k, const float* bias, int D, int L, int bidirectional,
                        void* kspec, void* ws, size_t ws_bytes, void* stream);
 /* uspec (may be NULL): receives the spectrum of the padded input, ceil(B/2)*D*4L floats, for
